@@ -12,13 +12,18 @@ Measures the BASELINE.json headline metric ("TSBS DevOps: ingest rows/sec
      once and replayed (exactly TSBS methodology: tsbs_load replays a
      pre-generated data file); every replayed row is fully re-parsed,
      re-WAL-written and re-appended.
-  2. QUERY SUITE (after the timed region, reported in config.queries):
-     the 16-query TSBS DevOps suite on a scale=4000 / 72h ≈ 104M-row
-     device-resident fixture (reference's own benchmark config,
-     docs/benchmarks/tsbs/v0.12.0.md) — p50 over --query-reps runs.
+  2. QUERY SUITE (--full only; after the timed region, reported in
+     config.queries): the 16-query TSBS DevOps suite on a scale=4000 /
+     72h ≈ 104M-row device-resident fixture (reference's own benchmark
+     config, docs/benchmarks/tsbs/v0.12.0.md) — p50 over --query-reps runs.
+
+A plain run sets up, warms up, times the K steps and prints the result
+line; everything else the benchmark measures sits behind --full.
+--dump-outputs DIR writes what the ingest path left in the engine after
+the last timed step (see dump_outputs) so two builds can be compared.
 
 Contract (driver):
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 N>1 is launched by the driver via torch.distributed.run (one rank per GPU,
 RCCL). Weak scaling: each rank ingests its own disjoint host shard and
 holds a hash shard of the scale-4000 query fixture. Rank 0 prints ONE JSON
@@ -45,6 +50,71 @@ BASELINE_INGEST = 326_839.28   # rows/s, reference v0.12.0
 def log(msg):
     if int(os.environ.get("RANK", "0")) == 0:
         print(msg, flush=True)
+
+
+DUMP_SEED = 20260912           # fixed host sample for --dump-outputs
+DUMP_HOSTS = 8
+DUMP_EPOCHS = 60               # sampled time window: first 60 points/host
+DUMP_MAX_ROWS = 500_000        # x 12 float64 columns = 48 MB, under 64 MB
+
+
+def dump_outputs(out_dir, eng, world, rank, n_workers, scale):
+    """Write what the timed ingest path produced — the table a client sees
+    after the last timed step — as float64 .npy files:
+
+      host_rows.npy      [H]      stored row count per host (hosts sorted
+                                  by name)
+      host_field_min.npy [H, 10]  per-host min of every usage_* field
+      host_field_max.npy [H, 10]  per-host max of every usage_* field
+      sample_rows.npy    [n, 12]  every stored row of a fixed, seeded host
+                                  sample inside a fixed time window:
+                                  (sample host index, ts ms, 10 fields),
+                                  sorted on all columns
+
+    All four are order-independent functions of the stored rows, so they
+    do not depend on thread interleaving or flush timing. With world > 1
+    every rank dumps its own engine as <name>.rank<r>.npy."""
+    from greptimedb_amd.models.tsbs import CPU_FIELDS
+    from greptimedb_amd.query.executor import Executor
+
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f".rank{rank}" if world > 1 else ""
+    ex = Executor(eng)
+    aggs = ", ".join(f"min({f}), max({f})" for f in CPU_FIELDS)
+    r = ex.execute(f"SELECT hostname, count(*), {aggs} FROM cpu "
+                   f"GROUP BY hostname ORDER BY hostname")
+    cols = [np.asarray(c, dtype=np.float64) for c in r.columns[1:]]
+    outs = {"host_rows": cols[0],
+            "host_field_min": np.stack(cols[1::2], axis=1),
+            "host_field_max": np.stack(cols[2::2], axis=1)}
+
+    rng = np.random.RandomState(DUMP_SEED)
+    universe = world * n_workers * scale
+    picks = rng.choice(universe, size=min(DUMP_HOSTS, universe), replace=False)
+    names = []
+    for p in sorted(int(p) for p in picks):
+        rk, rest = divmod(p, n_workers * scale)
+        wi, h = divmod(rest, scale)
+        names.append(f"host_{rk}_{wi}_{h}")
+    from greptimedb_amd.models.tsbs_fixture import INTERVAL_MS, START_TS_S
+    lo = START_TS_S * 1000
+    hi = lo + DUMP_EPOCHS * INTERVAL_MS
+    in_list = ", ".join(f"'{n}'" for n in names)
+    r = ex.execute(f"SELECT hostname, ts, {', '.join(CPU_FIELDS)} FROM cpu "
+                   f"WHERE hostname IN ({in_list}) AND ts >= {lo} AND ts < {hi}")
+    host_idx = {n: i for i, n in enumerate(names)}
+    rows = np.empty((len(r), 2 + len(CPU_FIELDS)), dtype=np.float64)
+    if len(r):
+        rows[:, 0] = [host_idx[h] for h in r.columns[0]]
+        for j, c in enumerate(r.columns[1:]):
+            rows[:, 1 + j] = np.asarray(c, dtype=np.float64)
+        rows = rows[np.lexsort(rows.T[::-1])]
+    outs["sample_rows"] = rows[:DUMP_MAX_ROWS]
+    for name, arr in outs.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"),
+                np.ascontiguousarray(arr, dtype=np.float64))
+    log(f"# dumped outputs to {out_dir}: " + ", ".join(
+        f"{k}{list(v.shape)}" for k, v in outs.items()))
 
 
 def main():
@@ -85,11 +155,20 @@ def main():
                     help="fixture time span (default 72h on GPU = 104M rows)")
     ap.add_argument("--query-reps", type=int, default=7)
     ap.add_argument("--skip-queries", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: "
+                         "the TSBS query suite on the scale-4000 fixture "
+                         "(config.queries)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the stored table's "
+                         "per-host aggregates and a seeded row sample as "
+                         "DIR/<name>.npy (float64)")
     ap.add_argument("--no-route", action="store_true",
                     help="diagnostic: pre-sharded ingest (no cross-rank "
                          "fan-out); NOT the default because any-rank "
                          "routing is the honest distributed path")
     args = ap.parse_args()
+    start0 = time.perf_counter()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -201,6 +280,8 @@ def main():
         for t in threads:
             t.join()
 
+    log(f"# setup: {time.perf_counter() - start0:.1f}s")
+
     # ---------------- warmup ----------------
     run_steps(0, args.warmup)
     barrier_sync()
@@ -230,22 +311,40 @@ def main():
     log(f"# ingest: {total_rows} rows in {elapsed:.1f}s = "
         f"{rows_per_s:,.0f} rows/s (stored {ingest_rows_stored}, "
         f"{n_ssts} SSTs live)")
-    # drain background flush/compaction before tearing the engine down so
-    # rmtree doesn't race the flusher thread
+    # quiesce background flush/compaction before tearing the engine down so
+    # rmtree doesn't race the flusher thread. A plain run drops the flushes
+    # still queued (the timed region is over; unflushed rows stay scannable
+    # in the memtables) and eng.close() waits only for the one in progress;
+    # --full drains the whole backlog before the query suite
     drain0 = time.perf_counter()
-    while not eng._flush_q.empty() and time.perf_counter() - drain0 < 120:
-        time.sleep(0.2)
+    if args.full:
+        while not eng._flush_q.empty() and time.perf_counter() - drain0 < 120:
+            time.sleep(0.2)
+    else:
+        import queue
+        try:
+            while True:
+                eng._flush_q.get_nowait()
+        except queue.Empty:
+            pass
+    drain_s = time.perf_counter() - drain0
     if exchange is not None:
         import torch.distributed as dist
         dist.barrier()  # all remote applies acked everywhere
         exchange.close()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, world, rank, n_workers,
+                     args.scale)
+    close0 = time.perf_counter()
     eng.close()
     shutil.rmtree(data_dir, ignore_errors=True)
+    log(f"# teardown: flush drain {drain_s:.1f}s, close + cleanup "
+        f"{time.perf_counter() - close0:.1f}s")
 
     # -------- query suite on the reference benchmark config (scale=4000) ----
     queries = {}
     q_meta = {}
-    if not args.skip_queries:
+    if args.full and not args.skip_queries:
         from greptimedb_amd.models.tsbs_fixture import load_cpu_fixture, tsbs_queries
         from greptimedb_amd.parallel.dist import DistContext
         qdir = os.path.join(base, f"qrank{rank}")

@@ -103,9 +103,15 @@ class CpuWorkload:
         vals = self.values[idx]  # (n, nf)
         lines = []
         fields = CPU_FIELDS
+        # a host's values are constant within one batch: format them once
+        # per host, not once per row
+        prefix: dict[int, bytes] = {}
         for r in range(n_rows):
-            h = idx[r]
-            fv = vals[r]
-            fstr = ",".join(f"{fields[j]}={fv[j]:.4f}" for j in range(len(fields)))
-            lines.append(b"cpu," + self.tagsets[h] + b" " + fstr.encode() + b" " + str(ts[r]).encode())
+            h = int(idx[r])
+            head = prefix.get(h)
+            if head is None:
+                fv = vals[r]
+                fstr = ",".join(f"{fields[j]}={fv[j]:.4f}" for j in range(len(fields)))
+                head = prefix[h] = b"cpu," + self.tagsets[h] + b" " + fstr.encode() + b" "
+            lines.append(head + str(ts[r]).encode())
         return b"\n".join(lines) + b"\n"

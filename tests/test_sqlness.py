@@ -12,7 +12,7 @@ import os
 import numpy as np
 import pytest
 
-CASES_DIR = os.path.join(os.path.dirname(__file__), "cases")
+CASES_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "cases")
 
 
 def _fmt_value(v):
@@ -48,7 +48,9 @@ def run_case(path, engine):
 
 @pytest.mark.parametrize("case", sorted(glob.glob(f"{CASES_DIR}/*.sql")),
                          ids=lambda p: os.path.basename(p))
-def test_golden_case(case, tmp_engine):
+def test_golden_case(case, tmp_engine, tmp_path, monkeypatch):
+    # cases name files (COPY TO/FROM) by relative path: keep them in tmp_path
+    monkeypatch.chdir(tmp_path)
     got = run_case(case, tmp_engine)
     golden = case.replace(".sql", ".result")
     assert os.path.exists(golden), f"missing golden {golden}; run --update"
@@ -60,9 +62,9 @@ if __name__ == "__main__":
     import tempfile
     repo_root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     sys.path.insert(0, repo_root)
-    os.chdir(repo_root)  # engines resolve relative paths against the root
     from greptimedb_amd.engine.engine import EngineConfig, MitoEngine
     for case in sorted(glob.glob(f"{CASES_DIR}/*.sql")):
+        os.chdir(tempfile.mkdtemp())  # files a case writes stay out of the repo
         eng = MitoEngine(EngineConfig(data_dir=tempfile.mkdtemp(), device="cpu",
                                       background_flush=False))
         open(case.replace(".sql", ".result"), "w").write(run_case(case, eng))
