@@ -88,6 +88,9 @@ std::vector<torch::Tensor> ts_bucket_agg(
     minmax_init_min = torch::full({nf, n_slots, n_buckets}, -1, opts_i64);
     minmax_init_max = torch::zeros({nf, n_slots, n_buckets}, opts_i64);
   }
+  // an empty source contributes nothing: hand back the (possibly passed-in)
+  // accumulators without a launch (a zero-row launch has a zero-sized grid)
+  if (n == 0) return {sum, cnt, minmax_init_min, minmax_init_max, rows};
   auto stream = at::cuda::getCurrentHIPStream().stream();
   auto cell = torch::empty({n}, ts.options().dtype(torch::kInt32));
   gdb_hip::launch_bucket_agg2(

@@ -37,6 +37,15 @@ DEV_INLINE double key_to_f64(uint64_t key) {
   return __longlong_as_double(bits);
 }
 
+// Bucket index = floor((t - origin) / bucket_ms), as cpu_ref defines it.
+// C++ '/' truncates toward zero, which would fold origin-bucket_ms < t <
+// origin into bucket 0; every t < origin floors below 0 (bucket_ms > 0), so
+// it maps to -1 and callers drop it with their b < 0 test.
+DEV_INLINE int64_t bucket_index(int64_t t, int64_t origin, int64_t bucket_ms) {
+  const int64_t d = t - origin;
+  return d < 0 ? -1 : d / bucket_ms;
+}
+
 // ---------------------------------------------------------------- K1+K2+K5
 // fields: column-major per field: fields[f * field_stride + row]
 // out arrays: [nf, n_slots, n_buckets]
@@ -62,7 +71,7 @@ __global__ void ts_bucket_agg_kernel(
     if (s < 0 || s >= lut_size) continue;
     const int32_t slot = slot_lut[s];
     if (slot < 0) continue;
-    int64_t b = (t - origin) / bucket_ms;
+    int64_t b = bucket_index(t, origin, bucket_ms);
     if (b < 0 || b >= n_buckets) continue;
     const int64_t cell0 = (int64_t)slot * n_buckets + b;
     atomicAdd(&out_rows[cell0], 1ULL);
@@ -165,7 +174,7 @@ __global__ void bucket_cell_kernel(
       if (t >= ts_lo && t < ts_hi && s >= 0 && s < lut_size) {
         const int32_t slot = slot_lut[s];
         if (slot >= 0) {
-          const int64_t b = (t - origin) / bucket_ms;
+          const int64_t b = bucket_index(t, origin, bucket_ms);
           if (b >= 0 && b < n_buckets) cl = slot * n_buckets + (int32_t)b;
         }
       }
@@ -264,7 +273,7 @@ __global__ void bucket_cell_coalesced_kernel(
     if (t >= ts_lo && t < ts_hi && sId >= 0 && sId < lut_size) {
       const int32_t slot = slot_lut[sId];
       if (slot >= 0) {
-        const int64_t b = (t - origin) / bucket_ms;
+        const int64_t b = bucket_index(t, origin, bucket_ms);
         if (b >= 0 && b < n_buckets) cl = slot * n_buckets + (int32_t)b;
       }
     }
@@ -745,8 +754,11 @@ void launch_bucket_agg2(
       ts, series, slot_lut, lut_size, ts_lo, ts_hi, origin, bucket_ms,
       n_buckets, n, cell_buf);
   {
+    // Tiles beyond the grid are taken by the kernel's tile grid-stride loop
+    // (only past 8192 tiles = 67M rows, too large for the test suite).
+    // n == 0 would give a zero-sized grid, which HIP rejects: clamp to 1.
     const int64_t ntiles = (n + AGG_TILE - 1) / AGG_TILE;
-    const int grid = (int)min(ntiles, (int64_t)8192);
+    const int grid = (int)max(min(ntiles, (int64_t)8192), (int64_t)1);
     hipLaunchKernelGGL(field_bucket_agg_lds_kernel,
         dim3(grid), dim3(256), 0, stream,
         cell_buf, fields, field_stride, field_idx, nf, n,

@@ -18,7 +18,9 @@ val_mode 0: payload = bits(val[i]) XOR bits(val[0]) (classic Gorilla).
 val_mode 1: values are integral at scale 10^k (metrics emitted with fixed
 decimals — the TSBS shape): payload = zigzag(int(val[i]*10^k) − base_int),
 base_val_bits holds the scaled int64 base. Delta widths beat XOR by ~4×
-on quantized walks. A column's ts is packed ONCE (ts-only block set);
+on quantized walks. Mode 1 is chosen only when it reproduces every value of
+the column bit-for-bit; otherwise the column is XOR-coded, so the codec is
+always lossless. A column's ts is packed ONCE (ts-only block set);
 field blocks carry ts_bits=0.
 """
 
@@ -49,15 +51,21 @@ def _bit_width(vals: np.ndarray) -> int:
 
 
 def _detect_scale(v: np.ndarray) -> int | None:
-    """Smallest k ≤ 4 with v·10^k integral (and in int48 range) or None."""
-    if not np.isfinite(v).all():
+    """Smallest k ≤ 4 at which the scaled-int codec is lossless for the whole
+    column: int(rint(v·10^k)) / 10^k — exactly what the decoders compute —
+    reproduces every value bit-for-bit (and fits int48). None otherwise, so
+    values that are merely close to the decimal grid (0.1+0.2), and -0.0,
+    fall back to the bit-exact XOR mode."""
+    if v.size == 0 or not np.isfinite(v).all():
         return None
+    bits = v.view(np.uint64)
     for k in (0, 1, 2, 3, 4):
-        sv = v * (10.0 ** k)
+        scale = 10.0 ** k
+        sv = v * scale
         if np.abs(sv).max() >= (1 << 47):
             return None
-        r = np.rint(sv)
-        if np.max(np.abs(sv - r)) < 1e-9 * max(1.0, np.abs(sv).max()):
+        back = np.rint(sv).astype(np.int64) / scale
+        if np.array_equal(back.view(np.uint64), bits):
             return k
     return None
 

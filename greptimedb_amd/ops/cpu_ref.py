@@ -160,9 +160,11 @@ def prom_range_eval(ts, vals, seg_lo, seg_hi, T, t0, step_ms, range_ms,
                 elif mode == 4:
                     r = w.mean()
                 elif mode == 6:
-                    r = w.min()
+                    # Prometheus min/max_over_time skip NaN samples; the
+                    # result is NaN only when every sample is NaN
+                    r = np.fmin.reduce(w)
                 elif mode == 7:
-                    r = w.max()
+                    r = np.fmax.reduce(w)
                 else:
                     var = ((w - w.mean()) ** 2).mean()
                     r = var if mode == 17 else np.sqrt(var)

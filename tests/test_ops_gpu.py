@@ -299,6 +299,9 @@ def test_k20_gorilla_gpu_decode_matches_ref():
         np.testing.assert_array_equal(v_g.cpu().numpy(), v_c.numpy())
         np.testing.assert_array_equal(ts_c.numpy(), ts)
         np.testing.assert_array_equal(v_c.numpy(), vals)
+        # the codec is lossless: bit patterns, not just values
+        np.testing.assert_array_equal(v_g.cpu().numpy().view(np.uint64),
+                                      vals.view(np.uint64))
 
 
 @pytest.mark.gpu
