@@ -3,8 +3,11 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <vector>
+
+#include "scatter_packed.h"
 
 namespace gdb_hip {
 void launch_ts_bucket_agg(
@@ -38,6 +41,8 @@ void launch_scatter_append(
     const int64_t*, const int32_t*, const double*, const int32_t*,
     const int64_t*, int64_t* const*, int32_t* const*, double* const*,
     const int64_t*, int, int64_t, hipStream_t);
+void launch_scatter_append_packed(
+    const unsigned char*, int64_t, int, const PackedRegions&, hipStream_t);
 void launch_rle_expand_indices(const int64_t*, int64_t, const uint8_t*, int,
                                int32_t*, int64_t, hipStream_t);
 void launch_gorilla_decode(const uint8_t*, const int64_t*, const int64_t*,
@@ -238,6 +243,76 @@ void scatter_append(
       pbase + 3 * R, nf, n, stream);
 }
 
+// K16, packed form: upload one routed batch with ONE non-blocking copy of
+// the used prefix of a pinned host block, then scatter it into the region
+// memtables with one launch; destinations go by value as kernel arguments.
+// Block layout (8-byte aligned segments, see csrc/ingest_core.h):
+//   ts i64[n] | fields f64[nf*n] | dst_off i64[n] | series i32[n] | region i32[n]
+// Row i lands at bases[region[i]] + dst_off[i]. Copy and kernel run on the
+// current stream; the caller must not refill `stage_pinned` before work
+// queued here has finished (it records an event after this call).
+void scatter_append_packed(
+    torch::Tensor stage_pinned, torch::Tensor stage_dev, int64_t n, int64_t nf,
+    std::vector<int64_t> bases, std::vector<torch::Tensor> dst_ts,
+    std::vector<torch::Tensor> dst_se, std::vector<torch::Tensor> dst_fields) {
+  TORCH_CHECK(!stage_pinned.is_cuda() && stage_pinned.is_pinned(),
+              "stage_pinned must be pinned host memory");
+  CHECK_GPU(stage_dev); CHECK_CONTIG(stage_pinned); CHECK_CONTIG(stage_dev);
+  TORCH_CHECK(stage_pinned.scalar_type() == torch::kUInt8 &&
+              stage_dev.scalar_type() == torch::kUInt8, "stage blocks are uint8");
+  TORCH_CHECK(n >= 0 && nf >= 0);
+  if (n == 0) return;
+  const int R = (int)dst_ts.size();
+  TORCH_CHECK(R >= 1 && R <= gdb_hip::kPackedRegions,
+              "scatter_append_packed handles 1..16 regions, got ", R);
+  TORCH_CHECK((int)bases.size() == R && (int)dst_se.size() == R &&
+              (int)dst_fields.size() == R, "per-region lists differ in length");
+  const int64_t i32_bytes = (4 * n + 7) & ~(int64_t)7;
+  const int64_t off_dst = 8 * n + 8 * nf * n;
+  const int64_t off_region = off_dst + 8 * n + i32_bytes;
+  const int64_t used = off_region + i32_bytes;
+  TORCH_CHECK(used <= stage_pinned.numel() && used <= stage_dev.numel(),
+              "stage block smaller than the batch");
+  gdb_hip::PackedRegions regs;
+  std::vector<int64_t> room(R);
+  for (int r = 0; r < gdb_hip::kPackedRegions; r++) {
+    regs.ts[r] = nullptr; regs.se[r] = nullptr; regs.f[r] = nullptr;
+    regs.stride[r] = 0; regs.base[r] = 0;
+  }
+  for (int r = 0; r < R; r++) {
+    CHECK_GPU(dst_ts[r]); CHECK_GPU(dst_se[r]); CHECK_GPU(dst_fields[r]);
+    CHECK_CONTIG(dst_ts[r]); CHECK_CONTIG(dst_se[r]); CHECK_CONTIG(dst_fields[r]);
+    TORCH_CHECK(dst_fields[r].dim() == 2 && dst_fields[r].size(0) >= nf,
+                "region ", r, " has fewer field rows than the batch");
+    TORCH_CHECK(bases[r] >= 0);
+    regs.ts[r] = dst_ts[r].data_ptr<int64_t>();
+    regs.se[r] = dst_se[r].data_ptr<int32_t>();
+    regs.f[r] = dst_fields[r].data_ptr<double>();
+    regs.stride[r] = dst_fields[r].size(1);
+    regs.base[r] = bases[r];
+    room[r] = std::min(std::min(dst_ts[r].numel(), dst_se[r].numel()),
+                       dst_fields[r].size(1));
+  }
+  // every destination row is checked on the host before anything is queued
+  const uint8_t* hp = stage_pinned.data_ptr<uint8_t>();
+  const int64_t* h_dst = reinterpret_cast<const int64_t*>(hp + off_dst);
+  const int32_t* h_region = reinterpret_cast<const int32_t*>(hp + off_region);
+  for (int64_t i = 0; i < n; i++) {
+    const int32_t r = h_region[i];
+    TORCH_CHECK(r >= 0 && r < R, "row ", i, ": region ", r, " out of range");
+    TORCH_CHECK(h_dst[i] >= 0 && bases[r] + h_dst[i] < room[r],
+                "row ", i, ": destination row beyond region ", r, " capacity");
+  }
+  auto stream = at::cuda::getCurrentHIPStream().stream();
+  const hipError_t err = hipMemcpyAsync(
+      stage_dev.data_ptr<uint8_t>(), hp, (size_t)used, hipMemcpyHostToDevice, stream);
+  TORCH_CHECK(err == hipSuccess, "stage upload failed: ", hipGetErrorString(err));
+  gdb_hip::launch_scatter_append_packed(
+      stage_dev.data_ptr<uint8_t>(), n, (int)nf, regs, stream);
+  const hipError_t lerr = hipGetLastError();
+  TORCH_CHECK(lerr == hipSuccess, "scatter_append_packed launch failed: ",
+              hipGetErrorString(lerr));
+}
 
 // K11: parquet hybrid RLE/bit-packed dictionary indices → i32 on device.
 // runs: i64[R,5] (host-built, csrc/pagedec.cpp), blob: u8 device tensor
@@ -284,4 +359,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("series_last_row", &series_last_row, "per-slot winner row (lastpoint)");
   m.def("prom_range_eval", &prom_range_eval, "PromQL range-vector evaluator");
   m.def("scatter_append", &scatter_append, "bulk routed memtable append (K16)");
+  m.def("scatter_append_packed", &scatter_append_packed,
+        "K16 from one packed pinned block: one H2D copy + one launch");
 }

@@ -23,6 +23,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "scatter_packed.h"
+
 #define DEV_INLINE __device__ __forceinline__
 
 namespace gdb_hip {
@@ -690,6 +692,45 @@ __global__ void scatter_append_kernel(
   }
 }
 
+// Packed form of K16: the whole routed batch arrives as ONE block (layout of
+// gdb_ingest::StageLayout in csrc/ingest_core.h, every segment 8-byte
+// aligned):
+//   ts i64[n] | fields f64[nf*n] | dst_off i64[n] | series i32[n] | region i32[n]
+// and the per-region destinations travel by value in the kernel arguments,
+// so a batch costs one H2D copy and one launch with no pointer-table upload.
+// Row i lands at base[region[i]] + dst_off[i]. Work items run over
+// (column, row) with row fastest: column 0 writes ts + series, column 1 + f
+// writes field f — reads stay coalesced along the row axis and rows of one
+// region write neighbouring addresses.
+__global__ void scatter_append_packed_kernel(
+    const unsigned char* __restrict__ stage, int64_t n, int nf,
+    const PackedRegions regs) {
+  const int64_t* __restrict__ ts = reinterpret_cast<const int64_t*>(stage);
+  const double* __restrict__ fields = reinterpret_cast<const double*>(stage + 8 * n);
+  const int64_t* __restrict__ dst_off =
+      reinterpret_cast<const int64_t*>(stage + 8 * n + 8 * (int64_t)nf * n);
+  const int64_t i32_bytes = (4 * n + 7) & ~(int64_t)7;
+  const unsigned char* sbase = stage + 16 * n + 8 * (int64_t)nf * n;
+  const int32_t* __restrict__ series = reinterpret_cast<const int32_t*>(sbase);
+  const int32_t* __restrict__ region = reinterpret_cast<const int32_t*>(sbase + i32_bytes);
+  const int64_t total = n * (int64_t)(nf + 1);
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+       idx += stride) {
+    const int64_t col = idx / n;
+    const int64_t i = idx - col * n;
+    const int r = region[i];
+    const int64_t o = regs.base[r] + dst_off[i];
+    if (col == 0) {
+      regs.ts[r][o] = ts[i];
+      regs.se[r][o] = series[i];
+    } else {
+      const int64_t f = col - 1;
+      regs.f[r][f * regs.stride[r] + o] = fields[f * n + i];
+    }
+  }
+}
+
 // ---------------------------------------------------------------- launchers
 
 static inline int grid_for(int64_t n, int block) {
@@ -775,6 +816,14 @@ void launch_scatter_append(
   hipLaunchKernelGGL(scatter_append_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream,
       ts, series, fields, region_of, dst_off, ts_ptrs, se_ptrs, f_ptrs,
       strides, nf, n);
+}
+
+void launch_scatter_append_packed(
+    const unsigned char* stage, int64_t n, int nf, const PackedRegions& regs,
+    hipStream_t stream) {
+  hipLaunchKernelGGL(scatter_append_packed_kernel,
+      dim3(grid_for(n * (int64_t)(nf + 1), 256)), dim3(256), 0, stream,
+      stage, n, nf, regs);
 }
 
 void launch_series_last(

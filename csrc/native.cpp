@@ -26,6 +26,8 @@
 #include <unordered_map>
 #include <vector>
 
+#include "ingest_core.h"
+
 namespace py = pybind11;
 
 // ------------------------------------- crc32 (IEEE, zlib-compatible, slice-by-8)
@@ -62,222 +64,188 @@ static uint32_t crc32_update(uint32_t crc, const uint8_t* buf, size_t len) {
   return ~crc;
 }
 
-// ---------------------------------------------------------------- LineParser
-
-struct ParseResult {
-  std::vector<int32_t> series;
-  std::vector<int64_t> ts;
-  // field columns, lazily NaN-padded
-  std::vector<std::vector<double>> cols;
-  std::vector<std::pair<int32_t, std::string>> new_tagsets;
-};
-
-// FNV-1a 64-bit over a byte range (tagset / field-name interning probe).
+// FNV-1a 64-bit over a byte range (interning probe of the prom/otlp parsers
+// and the tokenizer; the line parser hashes a word at a time, ingest_core.h).
 static inline uint64_t fnv1a(const char* p, size_t n) {
   uint64_t h = 1469598103934665603ULL;
   for (size_t i = 0; i < n; i++) { h ^= (uint8_t)p[i]; h *= 1099511628211ULL; }
   return h;
 }
 
-// Fast decimal parse for the common "[-]digits[.digits]" shape; falls back to
-// strtod for exponents/inf/nan.
-static inline double fast_atof(const char* p, const char* end) {
-  bool neg = false;
-  const char* s = p;
-  if (s < end && (*s == '-' || *s == '+')) { neg = (*s == '-'); s++; }
-  uint64_t ip = 0; int nd = 0;
-  while (s < end && *s >= '0' && *s <= '9' && nd < 18) { ip = ip * 10 + (*s - '0'); s++; nd++; }
-  double v = (double)ip;
-  if (s < end && *s == '.') {
-    s++;
-    uint64_t fp = 0; int fd = 0;
-    while (s < end && *s >= '0' && *s <= '9' && fd < 18) { fp = fp * 10 + (*s - '0'); s++; fd++; }
-    static const double pow10[19] = {1e0,1e1,1e2,1e3,1e4,1e5,1e6,1e7,1e8,1e9,1e10,
-                                     1e11,1e12,1e13,1e14,1e15,1e16,1e17,1e18};
-    v += (double)fp / pow10[fd];
-  }
-  if (s < end && (*s == 'e' || *s == 'E')) return strtod(p, nullptr);  // rare
-  return neg ? -v : v;
-}
+// ---------------------------------------------------------------- LineParser
+// pybind glue over gdb_ingest::LineCore / fused_ingest (csrc/ingest_core.h).
 
-static inline int64_t fast_atoll(const char* p, const char* end) {
-  bool neg = false;
-  if (p < end && (*p == '-' || *p == '+')) { neg = (*p == '-'); p++; }
-  int64_t v = 0;
-  while (p < end && *p >= '0' && *p <= '9') { v = v * 10 + (*p - '0'); p++; }
-  return neg ? -v : v;
+// numpy array over malloc'd memory that the array (and its views) own.
+static py::capsule owner_of(void* p) {
+  return py::capsule(p, [](void* q) { std::free(q); });
 }
 
 class LineParser {
  public:
   // Parse a batch of lines. Returns (series i32[n], ts i64[n],
-  // {field: f64[n]}, [(id, tagset_bytes)...new]).
+  // {field: f64[n]}, [(id, tagset_bytes)...new]). The field arrays are rows
+  // of one [F, n] block the parser wrote directly.
   py::tuple parse(py::bytes data) {
     char* buf;
     Py_ssize_t len;
     if (PyBytes_AsStringAndSize(data.ptr(), &buf, &len) != 0)
       throw std::runtime_error("expected bytes");
-    ParseResult r;
-    r.cols.resize(field_names_.size());
-    size_t nrows = 0;
+    gdb_ingest::ParseSink sink;
+    const size_t F0 = core_.num_fields();
+    size_t nrows = 0, est = 0;
+    int32_t* series = nullptr;
+    int64_t* ts = nullptr;
+    double* block = nullptr;
     {
       py::gil_scoped_release rel;  // pure C scan; enables threaded ingest workers
-      // estimate rows for reserve
-      size_t est = 0;
-      for (const char* q = buf; (q = static_cast<const char*>(
-               memchr(q, '\n', buf + len - q))) != nullptr; q++) est++;
-      est += 1;
-      r.series.reserve(est);
-      r.ts.reserve(est);
-      for (auto& c : r.cols) c.reserve(est);
-
-      const char* p = buf;
-      const char* end = buf + len;
-      while (p < end) {
-        const char* nl = static_cast<const char*>(memchr(p, '\n', end - p));
-        const char* line_end = nl ? nl : end;
-        if (line_end > p && *p != '#') {
-          parse_line(p, line_end, r, nrows);
-        }
-        p = nl ? nl + 1 : end;
+      est = gdb_ingest::LineCore::count_lines(buf, (size_t)len);
+      series = static_cast<int32_t*>(std::malloc(4 * est + 8));
+      ts = static_cast<int64_t*>(std::malloc(8 * est + 8));
+      block = static_cast<double*>(std::malloc(8 * est * F0 + 8));
+      if (series && ts && block) {
+        sink.series = series;
+        sink.ts = ts;
+        sink.cap = est;
+        sink.col.resize(F0);
+        for (size_t c = 0; c < F0; c++) sink.col[c] = block + c * est;
+        nrows = core_.parse(buf, (size_t)len, sink);
       }
     }
-
-    // materialize numpy outputs
-    py::array_t<int32_t> series(nrows);
-    py::array_t<int64_t> ts(nrows);
-    std::memcpy(series.mutable_data(), r.series.data(), nrows * 4);
-    std::memcpy(ts.mutable_data(), r.ts.data(), nrows * 8);
-    py::dict fields;
-    for (size_t c = 0; c < field_names_.size(); c++) {
-      auto& col = r.cols[c];
-      col.resize(nrows, std::nan(""));
-      py::array_t<double> a(nrows);
-      std::memcpy(a.mutable_data(), col.data(), nrows * 8);
-      fields[py::str(field_names_[c])] = std::move(a);
-    }
-    py::list newts;
-    for (auto& [id, s] : r.new_tagsets)
-      newts.append(py::make_tuple(id, py::bytes(s)));
-    return py::make_tuple(std::move(series), std::move(ts), std::move(fields), std::move(newts));
+    py::capsule so = owner_of(series), to = owner_of(ts), bo = owner_of(block);
+    if (!series || !ts || !block) throw std::bad_alloc();
+    return make_parse_tuple(
+        py::array_t<int32_t>({(py::ssize_t)nrows}, {4}, series, so),
+        py::array_t<int64_t>({(py::ssize_t)nrows}, {8}, ts, to),
+        sink, nrows, F0, bo);
   }
 
-  size_t num_series() const { return tagset_ids_.size(); }
-  std::vector<std::string> field_names() const { return field_names_; }
+  // Steady-state ingest in one GIL-released pass (gdb_ingest::fused_ingest):
+  // parse, route through the sid LUTs, build the packed row block in `stage`
+  // and the per-region WAL payloads. Returns
+  //   (0, n, counts, mins, maxs, [payload | None per region])   routed
+  //   (1, (series, ts, fields, new_tagsets))    general path, parse() tuple
+  //   (2, bytes_needed)                         stage too small; not parsed
+  py::tuple ingest_batch(
+      py::bytes data, py::array_t<int32_t, py::array::c_style> sid_region,
+      py::array_t<int32_t, py::array::c_style> sid_local,
+      py::array_t<int64_t, py::array::c_style> fmap, size_t n_parser_fields,
+      int n_regions, py::bytes hdr_suffix, bool durable, int64_t ts_scale,
+      py::array_t<uint8_t, py::array::c_style> stage) {
+    char* buf;
+    Py_ssize_t len;
+    if (PyBytes_AsStringAndSize(data.ptr(), &buf, &len) != 0)
+      throw std::runtime_error("expected bytes");
+    if (sid_region.ndim() != 1 || sid_local.ndim() != 1 || fmap.ndim() != 1 ||
+        stage.ndim() != 1 || sid_local.shape(0) != sid_region.shape(0))
+      throw std::runtime_error("ingest_batch: bad argument shapes");
+    char* sp = reinterpret_cast<char*>(stage.mutable_data());
+    if (reinterpret_cast<uintptr_t>(sp) % 8 != 0)
+      throw std::runtime_error("ingest_batch: stage must be 8-byte aligned");
+    const std::string suffix = hdr_suffix;
+    const size_t F0 = core_.num_fields();
+    auto* res = new gdb_ingest::FusedResult();
+    py::capsule keep(res, [](void* q) {
+      delete static_cast<gdb_ingest::FusedResult*>(q);
+    });
+    {
+      py::gil_scoped_release rel;
+      gdb_ingest::fused_ingest(
+          core_, buf, (size_t)len, sid_region.data(), sid_local.data(),
+          (size_t)sid_region.shape(0), fmap.data(), (int)fmap.shape(0),
+          n_parser_fields, n_regions, suffix, durable, ts_scale, sp,
+          (size_t)stage.shape(0), *res);
+    }
+    if (res->status == gdb_ingest::FUSED_GROW)
+      return py::make_tuple(2, res->need_bytes);
+    if (res->status == gdb_ingest::FUSED_SLOW) {
+      // hand the parse result over as fresh arrays (the stage is reused)
+      const size_t n = res->n;
+      py::array_t<int32_t> series((py::ssize_t)n);
+      py::array_t<int64_t> ts((py::ssize_t)n);
+      if (n) {
+        std::memcpy(series.mutable_data(), res->sink.series, 4 * n);
+        std::memcpy(ts.mutable_data(), res->sink.ts, 8 * n);
+      }
+      double* block = static_cast<double*>(std::malloc(8 * n * F0 + 8));
+      py::capsule bo = owner_of(block);
+      if (!block) throw std::bad_alloc();
+      for (size_t c = 0; c < F0 && n; c++)
+        std::memcpy(block + c * n, res->sink.col[c], 8 * n);
+      for (size_t c = 0; c < F0; c++) res->sink.col[c] = block + c * n;
+      return py::make_tuple(1, make_parse_tuple(
+          std::move(series), std::move(ts), res->sink, n, F0, bo));
+    }
+    py::array_t<int64_t> counts(n_regions), mins(n_regions), maxs(n_regions);
+    py::list payloads;
+    if (res->n) {
+      std::memcpy(counts.mutable_data(), res->counts.data(), 8 * (size_t)n_regions);
+      std::memcpy(mins.mutable_data(), res->mins.data(), 8 * (size_t)n_regions);
+      std::memcpy(maxs.mutable_data(), res->maxs.data(), 8 * (size_t)n_regions);
+      for (int r = 0; r < n_regions; r++) {
+        const size_t lo = res->wal_off[r], hi = res->wal_off[r + 1];
+        if (hi == lo) {
+          payloads.append(py::none());
+        } else {   // view into the result's WAL arena (kept alive by `keep`)
+          payloads.append(py::array_t<uint8_t>(
+              {(py::ssize_t)(hi - lo)}, {1},
+              reinterpret_cast<const uint8_t*>(res->wal.data() + lo), keep));
+        }
+      }
+    }
+    return py::make_tuple(0, res->n, std::move(counts), std::move(mins),
+                          std::move(maxs), std::move(payloads));
+  }
+
+  size_t num_series() const { return core_.num_series(); }
+  std::vector<std::string> field_names() const { return core_.field_names(); }
+  size_t num_fields() const { return core_.num_fields(); }
+  size_t intern_capacity() const { return core_.intern_capacity(); }
 
   py::bytes tagset_str(int32_t sid) const {
-    if (sid < 0 || (size_t)sid >= tagset_strs_.size())
-      throw std::out_of_range("unknown series ref");
-    return py::bytes(tagset_strs_[sid]);
+    const std::string* s = core_.tagset_str(sid);
+    if (!s) throw std::out_of_range("unknown series ref");
+    return py::bytes(*s);
   }
 
   // Restore dictionary state (e.g. after WAL replay / reopen).
-  void register_tagset(const std::string& s, int32_t id) {
-    tagset_ids_.emplace(fnv1a(s.data(), s.size()), id);
-    tagset_strs_.resize(std::max<size_t>(tagset_strs_.size(), id + 1));
-    tagset_strs_[id] = s;
-    next_id_ = std::max(next_id_, id + 1);
-  }
-  void register_field(const std::string& name) { field_idx(name.data(), name.size()); }
+  void register_tagset(const std::string& s, int32_t id) { core_.register_tagset(s, id); }
+  void register_field(const std::string& name) { core_.register_field(name); }
 
  private:
-  void parse_line(const char* p, const char* end, ParseResult& r, size_t& nrows) {
-    // measurement,tagset fieldset [timestamp]
-    // NOTE: influx escape sequences (\,, \ , \=) are not handled — TSBS and
-    // our writers never emit them; reject lines containing a backslash.
-    const char* sp1 = static_cast<const char*>(memchr(p, ' ', end - p));
-    if (!sp1) return;  // malformed
-    const char* sp2 = static_cast<const char*>(memchr(sp1 + 1, ' ', end - sp1 - 1));
-
-    // series key = "measurement,tagset" — interned via hash probe + byte
-    // verify (no per-row allocation on the hit path)
-    const size_t klen = sp1 - p;
-    const uint64_t h = fnv1a(p, klen);
-    int32_t sid = -1;
-    auto range = tagset_ids_.equal_range(h);
-    for (auto it = range.first; it != range.second; ++it) {
-      const std::string& s = tagset_strs_[it->second];
-      if (s.size() == klen && memcmp(s.data(), p, klen) == 0) { sid = it->second; break; }
-    }
-    if (sid < 0) {
-      sid = next_id_++;
-      tagset_ids_.emplace(h, sid);
-      tagset_strs_.resize(std::max<size_t>(tagset_strs_.size(), sid + 1));
-      tagset_strs_[sid].assign(p, klen);
-      r.new_tagsets.emplace_back(sid, tagset_strs_[sid]);
-    }
-
-    // timestamp (ns); missing timestamp → 0 (caller fills server time)
-    int64_t tsv = 0;
-    if (sp2) tsv = fast_atoll(sp2 + 1, end);
-
-    size_t row = nrows++;
-    r.series.push_back(sid);
-    r.ts.push_back(tsv);
-
-    // fieldset: k=v,k=v,...
-    const char* f = sp1 + 1;
-    const char* fend = sp2 ? sp2 : end;
-    size_t fpos = 0;
-    while (f < fend) {
-      const char* eq = static_cast<const char*>(memchr(f, '=', fend - f));
-      if (!eq) break;
-      const char* comma = static_cast<const char*>(memchr(eq + 1, ',', fend - eq - 1));
-      const char* vend = comma ? comma : fend;
-      double val;
-      const char* v = eq + 1;
-      if (v < vend && (*v == '"')) {
-        // string field value — not representable in the float column; store NaN.
-        val = std::nan("");
-      } else if (vend > v && (vend[-1] == 'i' || vend[-1] == 'u')) {
-        val = static_cast<double>(fast_atoll(v, vend - 1));
-      } else if (vend > v && (*v == 't' || *v == 'T' || *v == 'f' || *v == 'F')) {
-        val = (*v == 't' || *v == 'T') ? 1.0 : 0.0;
+  // (series, ts, {field: f64[n]}, new tagsets). Fields known before the
+  // batch are views of the [F0, stride] block that `block_owner` frees;
+  // fields first seen in the batch were parsed into sink.extra.
+  py::tuple make_parse_tuple(py::array_t<int32_t> series, py::array_t<int64_t> ts,
+                             gdb_ingest::ParseSink& sink, size_t n, size_t F0,
+                             py::capsule block_owner) {
+    const auto& names = core_.field_names();
+    py::dict fields;
+    for (size_t c = 0; c < names.size(); c++) {
+      if (c < F0 && c < sink.col.size()) {
+        fields[py::str(names[c])] = py::array_t<double>(
+            {(py::ssize_t)n}, {8}, sink.col[c], block_owner);
       } else {
-        val = fast_atof(v, vend);
+        py::array_t<double> a((py::ssize_t)n);
+        if (n) {
+          if (c < sink.col.size()) {
+            std::memcpy(a.mutable_data(), sink.col[c], 8 * n);
+          } else {
+            std::fill(a.mutable_data(), a.mutable_data() + n, std::nan(""));
+          }
+        }
+        fields[py::str(names[c])] = std::move(a);
       }
-      // positional field cache: batches of lines share a fieldset layout
-      // (TSBS and most collectors), so field j of each row is usually the
-      // same name — memcmp against the cached name skips hash+map
-      size_t c;
-      const size_t flen = eq - f;
-      if (fpos < fcache_.size() && fcache_[fpos].first == flen &&
-          memcmp(field_names_[fcache_[fpos].second].data(), f, flen) == 0) {
-        c = fcache_[fpos].second;
-      } else {
-        c = field_idx(f, flen);
-        if (fpos >= fcache_.size()) fcache_.resize(fpos + 1);
-        fcache_[fpos] = {flen, c};
-      }
-      fpos++;
-      if (c >= r.cols.size()) r.cols.resize(c + 1);
-      auto& col = r.cols[c];
-      if (col.size() < row) col.resize(row, std::nan(""));
-      if (col.size() == row) col.push_back(val); else col[row] = val;
-      f = comma ? comma + 1 : fend;
     }
+    py::list newts;
+    for (auto& [id, s] : sink.new_tagsets)
+      newts.append(py::make_tuple(id, py::bytes(s)));
+    return py::make_tuple(std::move(series), std::move(ts), std::move(fields),
+                          std::move(newts));
   }
 
-  size_t field_idx(const char* name, size_t len) {
-    const uint64_t h = fnv1a(name, len);
-    auto range = fmap_.equal_range(h);
-    for (auto it = range.first; it != range.second; ++it) {
-      const std::string& s = field_names_[it->second];
-      if (s.size() == len && memcmp(s.data(), name, len) == 0) return it->second;
-    }
-    size_t idx = field_names_.size();
-    fmap_.emplace(h, idx);
-    field_names_.emplace_back(name, len);
-    return idx;
-  }
-
-  std::unordered_multimap<uint64_t, int32_t> tagset_ids_;
-  std::vector<std::string> tagset_strs_;
-  int32_t next_id_ = 0;
-  std::unordered_multimap<uint64_t, size_t> fmap_;
-  std::vector<std::string> field_names_;
-  std::vector<std::pair<size_t, size_t>> fcache_;  // positional (len, idx)
+  gdb_ingest::LineCore core_;
 };
+
 
 // ---------------------------------------------------------------- WalWriter
 
@@ -301,10 +269,26 @@ class WalWriter {
   // Buffer one entry (group commit happens in commit()). The crc over the
   // payload runs without the GIL — it is the ingest path's biggest
   // GIL-held C++ cost otherwise (callers serialize via the python Wal lock).
-  void append(uint64_t region_id, uint64_t seq, py::bytes payload) {
+  // `payload` is bytes or any contiguous buffer (the fused ingest path hands
+  // over uint8 views of its payload arena).
+  void append(uint64_t region_id, uint64_t seq, py::object payload) {
     char* pbuf; Py_ssize_t plen;
-    if (PyBytes_AsStringAndSize(payload.ptr(), &pbuf, &plen) != 0)
-      throw std::runtime_error("payload must be bytes");
+    Py_buffer view;
+    bool have_view = false;
+    if (PyBytes_Check(payload.ptr())) {
+      if (PyBytes_AsStringAndSize(payload.ptr(), &pbuf, &plen) != 0)
+        throw std::runtime_error("payload must be bytes");
+    } else {
+      if (PyObject_GetBuffer(payload.ptr(), &view, PyBUF_SIMPLE) != 0)
+        throw py::error_already_set();
+      have_view = true;
+      pbuf = static_cast<char*>(view.buf);
+      plen = view.len;
+    }
+    struct Release {
+      Py_buffer* v;
+      ~Release() { if (v) PyBuffer_Release(v); }
+    } release{have_view ? &view : nullptr};
     py::gil_scoped_release rel;
     uint32_t body_len = 16 + static_cast<uint32_t>(plen);
     size_t off = buf_.size();
@@ -1423,6 +1407,13 @@ PYBIND11_MODULE(_native, m) {
   py::class_<LineParser>(m, "LineParser")
       .def(py::init<>())
       .def("parse", &LineParser::parse)
+      .def("ingest_batch", &LineParser::ingest_batch, py::arg("data"),
+           py::arg("sid_region"), py::arg("sid_local"), py::arg("fmap"),
+           py::arg("n_parser_fields"), py::arg("n_regions"),
+           py::arg("hdr_suffix"), py::arg("durable"), py::arg("ts_scale"),
+           py::arg("stage"))
+      .def("num_fields", &LineParser::num_fields)
+      .def("intern_capacity", &LineParser::intern_capacity)
       .def("num_series", &LineParser::num_series)
       .def("tagset_str", &LineParser::tagset_str)
       .def("field_names", &LineParser::field_names)

@@ -404,6 +404,94 @@ class MitoEngine:
                 cb(table.schema.name, lo, hi, n)
         return True
 
+    def write_regions_fused(self, table: TableState, slot, n: int, nf: int,
+                            counts, mins, maxs, payloads: list,
+                            durable: bool = True) -> None:
+        """K16 fast path fed by LineParser.ingest_batch: the routed batch
+        sits in one packed block (`slot.host`, layout of
+        ops.cpu_ref.packed_segments) next to ready WAL payloads and
+        per-region counts/min/max. Python appends the WAL entries, reserves
+        rows under the region locks and makes ONE device call.
+
+        slot.dev set: ops.scatter_append_packed — one non-blocking copy of
+        the pinned block plus one kernel on the current stream (on a CPU
+        engine the reference implementation reads the block in place); the
+        slot's event is recorded behind the launch so the owner can wait
+        before refilling the block. slot.dev None: the block is ordinary
+        host memory and its segments go through today's scatter_append.
+        The caller has checked that no region has text columns and that all
+        are writable."""
+        import torch
+        from greptimedb_amd.ops import cpu_ref
+        from greptimedb_amd.ops import kernels as ops
+
+        regions: list[Region] = table.regions
+        counts = [int(c) for c in counts]
+        seqs = [0] * len(regions)
+        if durable:
+            for k, p in enumerate(payloads):
+                if p is not None:
+                    seqs[k] = self.wal.append(regions[k].region_id, p)
+        ordered = sorted(regions, key=lambda r: r.region_id)
+        for r in ordered:
+            r.lock.acquire()
+        try:
+            bases = []
+            for k, region in enumerate(regions):
+                mem = region.memtable
+                if mem.nf < nf:
+                    mem.add_fields(nf - mem.nf)
+                need = mem.len + counts[k]
+                if need > mem.cap:
+                    mem._grow(need)
+                bases.append(mem.len)
+            dst_ts = [r.memtable.ts for r in regions]
+            dst_se = [r.memtable.series for r in regions]
+            dst_f = [r.memtable.fields for r in regions]
+            if slot.dev is not None:
+                ops.scatter_append_packed(slot.host, slot.dev, n, nf, bases,
+                                          dst_ts, dst_se, dst_f)
+                if slot.event is not None:
+                    slot.event.record()
+            else:
+                ts_h, f_h, do_h, se_h, ro_h = cpu_ref.packed_segments(
+                    slot.host, n, nf)
+                dev = self.config.device
+                dst = do_h + torch.tensor(bases, dtype=torch.int64)[ro_h.long()]
+                ops.scatter_append(ts_h.to(dev), se_h.to(dev), f_h.to(dev),
+                                   ro_h.to(dev), dst.to(dev),
+                                   dst_ts, dst_se, dst_f)
+            for k, region in enumerate(regions):
+                m = counts[k]
+                if m == 0:
+                    continue
+                mem = region.memtable
+                mem.len = bases[k] + m
+                mn, mx = int(mins[k]), int(maxs[k])
+                mem.min_ts = mn if mem.min_ts is None else min(mem.min_ts, mn)
+                mem.max_ts = mx if mem.max_ts is None else max(mem.max_ts, mx)
+                region.last_seq = max(region.last_seq, seqs[k])
+                region.row_seq += m
+        finally:
+            for r in reversed(ordered):
+                r.lock.release()
+        if (self.mirror_listeners or self.write_listeners) and n:
+            ts_h, f_h, _do, se_h, ro_h = (
+                t.numpy() for t in cpu_ref.packed_segments(slot.host, n, nf))
+            if self.mirror_listeners:
+                fnames = table.regions[0].field_names
+                for k, region in enumerate(regions):
+                    if counts[k] == 0:
+                        continue
+                    rows = np.flatnonzero(ro_h == k)
+                    for cb in self.mirror_listeners:
+                        cb(table, region, se_h[rows], ts_h[rows],
+                           f_h[:, rows], fnames)
+            if self.write_listeners:
+                lo, hi = int(np.min(ts_h)), int(np.max(ts_h))
+                for cb in self.write_listeners:
+                    cb(table.schema.name, lo, hi, n)
+
     def commit_wal(self):
         self.wal.commit()
 

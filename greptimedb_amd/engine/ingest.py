@@ -7,12 +7,32 @@ tagsets to dense sids; routing is two numpy LUT gathers (sid → flat region,
 sid → local code); per-region slices go to WAL then GPU memtable with ONE
 group commit per ingest batch (durability boundary, handle_write.rs:611).
 
+Steady state (bulk path, every row of a known series of one table) is ONE
+native call, LineParser.ingest_batch (csrc/ingest_core.h), with the GIL
+released: parse straight into a packed staging block, route each row through
+the per-table sid LUTs (region, local code, destination offset, ts → ms),
+and build the per-region WAL payloads. Python then only appends the WAL
+entries, reserves memtable rows under the region locks and makes one device
+call (engine.write_regions_fused → ops.scatter_append_packed: one
+non-blocking copy of the pinned block + one kernel), commits the WAL and
+checks flush thresholds. The staging blocks form a ring of STAGE_RING
+pinned/device pairs per Ingestor; an event recorded behind each launch is
+waited on before its block is refilled, so the host never overwrites a
+block its DMA has not read. Anything the native call cannot route — a new
+series or field, another table's rows, remote-owned series, more than 16
+regions, text columns — comes back as the ordinary parse() result and takes
+the general path below without being parsed twice. `Ingestor._fused = False`
+switches the whole fast path off; `_packed = False` keeps the fused pass but
+uploads the block's segments through scatter_append.
+
 Partitioning: hash(encoded pk) % n_regions (the default when no PARTITION ON
 clause — reference uses MultiDimPartitionRule; explicit partition rules live
 in parallel/partition.py).
 """
 
 from __future__ import annotations
+
+import weakref
 
 import numpy as np
 
@@ -32,6 +52,37 @@ def parse_tagset(key: bytes) -> tuple[str, list[tuple[str, str]]]:
             k, v = p.split("=", 1)
             tags.append((k, v))
     return measurement, tags
+
+
+STAGE_RING = 3            # staging blocks per Ingestor (>= 2)
+MAX_PACKED_REGIONS = 16   # region table size of scatter_append_packed
+
+
+class _StageSlot:
+    """One staging block of the fused path: `host` (uint8 tensor, pinned on
+    the packed GPU path) with its numpy view, the device block it uploads to
+    (the same tensor on a CPU engine, None when the segments go through
+    scatter_append) and the event recorded behind its last launch."""
+    __slots__ = ("host", "np", "dev", "event", "busy")
+
+    def __init__(self, host, dev, event):
+        self.host = host
+        self.np = host.numpy()
+        self.dev = dev
+        self.event = event
+        self.busy = False
+
+
+def _drain_ring(ring: list):
+    """Wait for the copies still reading the ring's pinned blocks (before
+    the blocks are freed or replaced)."""
+    for slot in ring:
+        if slot.event is not None and slot.busy:
+            try:
+                slot.event.synchronize()
+            except Exception:
+                pass   # interpreter shutdown: the runtime is already gone
+            slot.busy = False
 
 
 class Ingestor:
@@ -54,6 +105,18 @@ class Ingestor:
         # K16 bulk scatter-append: on by default on GPU (one kernel per batch
         # instead of per-region copy chains); CPU keeps the per-region path
         self._bulk = engine.config.device.startswith("cuda")
+        # fused native pass for the steady-state bulk batch (module docstring);
+        # off = today's parse → numpy routing → route_ingest path
+        self._fused = True
+        # packed device path: pinned staging ring + scatter_append_packed.
+        # Off on GPU = the stage is plain host memory and its segments go
+        # through scatter_append (CPU engines always read the block in place)
+        self._packed = True
+        self._ring: list[_StageSlot] = []   # staging ring, STAGE_RING slots
+        self._ring_pos = 0
+        self._fused_st = None    # table the fused LUTs describe
+        self._fused_lut = None   # (sid → table-local region | -1, sid → code)
+        weakref.finalize(self, _drain_ring, self._ring)
         # flat routing state, indexed by parser sid
         self._cap = 1024
         self.sid_region = np.full(self._cap, -1, dtype=np.int32)   # flat region idx
@@ -94,6 +157,7 @@ class Ingestor:
         nk[: len(self.sid_key)] = self.sid_key
         self.sid_key = nk
         self._cap = cap
+        self._fused_lut = None
 
     def _register_tagset(self, sid: int, key: bytes):
         """Cold path: new series — resolve table (auto-create), partition,
@@ -108,6 +172,7 @@ class Ingestor:
         tag_tuple = tuple(tag_map.get(t.name) for t in st.schema.tag_columns)
         if sid >= self._cap:
             self._grow(sid)
+        self._fused_lut = None
         self.sid_key[sid] = key
         if self.world > 1 and self.exchange is not None:
             owner = self._owner_of(st, tag_tuple)
@@ -190,13 +255,7 @@ class Ingestor:
         self._wal_suffix_cache[name] = (s, len(fn))
         return s
 
-    def ingest_lines(self, data: bytes, ts_scale_to_ns: int = 1) -> int:
-        """Parse + route + WAL + memtable-append one wire batch. Returns rows.
-        ts_scale_to_ns: multiplier for non-ns influx `precision` values."""
-        series, ts_ns, fields, new_tagsets = self.parser.parse(data)
-        n = len(series)
-        if n == 0:
-            return 0
+    def _check_epoch(self):
         # repartition invalidates routing: drop LUTs, re-resolve lazily
         epoch = getattr(self.engine, "routing_epoch", 0)
         if epoch != getattr(self, "_epoch", 0):
@@ -210,6 +269,117 @@ class Ingestor:
             self._table_field_map.clear()
             self._wal_suffix_cache.clear()
             self._flat_ridx_cache = None
+            self._fused_st = None
+            self._fused_lut = None
+
+    # ------------------------------------------------------ fused fast path
+
+    def _build_fused_lut(self, st0: TableState):
+        """sid → table-local region of `st0` (-1: unrouted, remote-owned or
+        another table's series) and sid → region-local code."""
+        flat_ridx = np.full(len(self.flat_regions) + 1, -1, dtype=np.int32)
+        for fi, (st_, ri) in enumerate(self.flat_regions):
+            if st_ is st0:
+                flat_ridx[fi] = ri
+        dense = flat_ridx[self.sid_region]   # -1 indexes the trailing -1
+        dense[self.sid_rank != self.rank] = -1
+        self._fused_lut = (np.ascontiguousarray(dense, dtype=np.int32),
+                           self.sid_local)
+        return self._fused_lut
+
+    def _grow_ring(self, need: int):
+        """(Re)allocate the staging ring so a batch of `need` bytes fits."""
+        import torch
+        _drain_ring(self._ring)   # no block is dropped with a copy in flight
+        nbytes = (need + need // 4 + 4095) & ~4095
+        dev = self.engine.config.device
+        on_gpu = dev.startswith("cuda")
+        slots = []
+        for _ in range(STAGE_RING):
+            if on_gpu and self._packed:
+                host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+                slot = _StageSlot(host, torch.empty(nbytes, dtype=torch.uint8,
+                                                    device=dev),
+                                  torch.cuda.Event())
+            else:
+                host = torch.empty(nbytes, dtype=torch.uint8)
+                slot = _StageSlot(host, None if on_gpu else host, None)
+            slots.append(slot)
+        self._ring[:] = slots
+        self._ring_pos = 0
+
+    def _next_slot(self) -> "_StageSlot":
+        """The ring block to fill next; waits (GIL released) until the copy
+        and kernel queued from its previous use have finished."""
+        slot = self._ring[self._ring_pos]
+        if slot.event is not None and slot.busy:
+            slot.event.synchronize()
+            slot.busy = False
+        return slot
+
+    def _ingest_fused(self, data: bytes, ts_scale_to_ns: int):
+        """Steady-state batch in one native call. Returns the row count when
+        the batch was written, else the parse() tuple for the general path."""
+        self._check_epoch()   # a repartition drops the LUTs before they route
+        st0 = self._fused_st
+        if st0 is None or self.engine.tables.get(st0.schema.name) is not st0:
+            return self.parser.parse(data)
+        regions = st0.regions
+        cached = self._table_field_map.get(st0.schema.name)
+        nparse = self.parser.num_fields()
+        if cached is None or cached[1] != nparse or \
+                len(cached[0]) != len(regions[0].field_names) or \
+                len(regions) > MAX_PACKED_REGIONS or \
+                any(r.text_cols or r.memtable.str_cols or not r.writable
+                    for r in regions):
+            return self.parser.parse(data)
+        lut = self._fused_lut or self._build_fused_lut(st0)
+        fmap = cached[0]
+        nf = len(fmap)
+        suffix = self._wal_suffix(st0)
+        if not self._ring:
+            self._grow_ring(1 << 16)
+        res = None
+        for _attempt in range(2):
+            slot = self._next_slot()
+            res = self.parser.ingest_batch(
+                data, lut[0], lut[1], fmap, nparse, len(regions), suffix,
+                self.durable, int(ts_scale_to_ns), slot.np)
+            if res[0] != 2:
+                break
+            self._grow_ring(int(res[1]))
+        if res[0] == 2:
+            raise RuntimeError("ingest stage block still too small after growing")
+        if res[0] == 1:
+            return res[1]
+        _, n, counts, mins, maxs, payloads = res
+        if n == 0:
+            return 0
+        engine = self.engine
+        engine.write_regions_fused(st0, slot, n, nf, counts, mins, maxs,
+                                   payloads, durable=self.durable)
+        slot.busy = slot.event is not None
+        self._ring_pos = (self._ring_pos + 1) % len(self._ring)
+        if self.durable:
+            engine.commit_wal()
+        engine.maybe_flush()
+        self.rows_ingested += n
+        return n
+
+    def ingest_lines(self, data: bytes, ts_scale_to_ns: int = 1) -> int:
+        """Parse + route + WAL + memtable-append one wire batch. Returns rows.
+        ts_scale_to_ns: multiplier for non-ns influx `precision` values."""
+        if self._bulk and self._fused:
+            got = self._ingest_fused(data, ts_scale_to_ns)
+            if isinstance(got, int):
+                return got
+            series, ts_ns, fields, new_tagsets = got
+        else:
+            series, ts_ns, fields, new_tagsets = self.parser.parse(data)
+        n = len(series)
+        if n == 0:
+            return 0
+        self._check_epoch()
         for sid, key in new_tagsets:
             self._register_tagset(sid, key)
         rank_of = self.sid_rank[series]
@@ -276,6 +446,9 @@ class Ingestor:
                    for f in flats}
             if len(sts) == 1:
                 st0 = next(iter(sts.values()))
+                if self._fused_st is not st0:   # next batch may go fused
+                    self._fused_st = st0
+                    self._fused_lut = None
                 fmap = self._field_map(st0, parser_fields, fields_mat,
                                        np.arange(n_local))
                 flat_ridx = self._flat_ridx_cache

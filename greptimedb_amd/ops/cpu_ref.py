@@ -250,3 +250,33 @@ def scatter_append(ts, series, fields, region_of, dst_off,
         dst_ts[r][o] = ts[m]
         dst_se[r][o] = series[m]
         dst_fields[r][:, o] = fields[:, m]
+
+
+def packed_segments(stage, n, nf):
+    """Views (ts i64[n], fields f64[nf, n], dst_off i64[n], series i32[n],
+    region i32[n]) into a packed stage block — a uint8 CPU tensor laid out
+    as csrc/ingest_core.h StageLayout (8-byte aligned segments)."""
+    pad4 = (4 * n + 7) & ~7
+    o_f = 8 * n
+    o_d = o_f + 8 * nf * n
+    o_s = o_d + 8 * n
+    o_r = o_s + pad4
+    ts = stage[:o_f].view(torch.int64)
+    fields = stage[o_f:o_d].view(torch.float64).reshape(nf, n)
+    dst_off = stage[o_d:o_s].view(torch.int64)
+    series = stage[o_s:o_s + 4 * n].view(torch.int32)
+    region = stage[o_r:o_r + 4 * n].view(torch.int32)
+    return ts, fields, dst_off, series, region
+
+
+def scatter_append_packed(stage_host, stage_dev, n, nf, bases,
+                          dst_ts, dst_se, dst_fields):
+    """Oracle for kernels.scatter_append_packed: row i of the packed block
+    goes to region region[i] at row bases[region[i]] + dst_off[i]. On CPU
+    there is no upload, so `stage_dev` is unused."""
+    if n == 0:
+        return
+    ts, fields, dst_off, series, region = packed_segments(stage_host, n, nf)
+    dst = dst_off + torch.as_tensor(list(bases), dtype=torch.int64)[region.long()]
+    scatter_append(ts, series, fields, region, dst, dst_ts, dst_se,
+                   [f[:nf] for f in dst_fields])

@@ -195,3 +195,20 @@ def scatter_append(ts, series, fields, region_of, dst_off,
         return
     cpu_ref.scatter_append(ts, series, fields, region_of, dst_off,
                            dst_ts, dst_se, dst_fields)
+
+
+def scatter_append_packed(stage_host, stage_dev, n, nf, bases,
+                          dst_ts, dst_se, dst_fields):
+    """K16 from one packed block (layout: cpu_ref.packed_segments). On GPU
+    `stage_host` is pinned: its used prefix goes to `stage_dev` with one
+    non-blocking copy on the current stream, then one kernel scatters row i
+    to region[i] at bases[region[i]] + dst_off[i]; the region table travels
+    in the kernel arguments (at most 16 regions). The caller must not refill
+    `stage_host` until work queued here has finished."""
+    if stage_dev.is_cuda:
+        _require_hip().scatter_append_packed(
+            stage_host, stage_dev, int(n), int(nf), [int(b) for b in bases],
+            list(dst_ts), list(dst_se), list(dst_fields))
+        return
+    cpu_ref.scatter_append_packed(stage_host, stage_dev, n, nf, bases,
+                                  dst_ts, dst_se, dst_fields)
