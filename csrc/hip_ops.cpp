@@ -4,7 +4,9 @@
 #include <ATen/hip/HIPContext.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
+#include <tuple>
 #include <vector>
 
 #include "scatter_packed.h"
@@ -47,6 +49,25 @@ void launch_rle_expand_indices(const int64_t*, int64_t, const uint8_t*, int,
                                int32_t*, int64_t, hipStream_t);
 void launch_gorilla_decode(const uint8_t*, const int64_t*, const int64_t*,
                            int64_t, int64_t*, double*, int64_t, hipStream_t);
+void launch_bucket_cells(
+    const int64_t*, const int32_t*, const int32_t*, int, int64_t, int64_t,
+    int64_t, int64_t, int, int64_t, int32_t*, hipStream_t);
+void launch_quantile_hist(
+    const int32_t*, const double*, int64_t, const int32_t*, int, const int32_t*,
+    int, int64_t, int, int, int, const unsigned long long*, unsigned int*,
+    hipStream_t);
+void launch_quantile_pick(
+    unsigned int*, const double*, int, int64_t, int, unsigned long long*,
+    int64_t*, int64_t*, int64_t*, hipStream_t);
+void launch_quantile_next(
+    const int32_t*, const double*, int64_t, const int32_t*, int, const int32_t*,
+    int, int64_t, int, int, const unsigned long long*, unsigned long long*,
+    unsigned long long*, hipStream_t);
+void launch_quantile_finish(
+    const unsigned long long*, const int64_t*, const int64_t*,
+    const unsigned long long*, const unsigned long long*, int64_t, double*,
+    double*, hipStream_t);
+void quantile_launch_config(int64_t out[3]);
 }  // namespace gdb_hip
 
 #define CHECK_GPU(x) TORCH_CHECK(x.is_cuda(), #x " must be on GPU")
@@ -344,6 +365,167 @@ std::vector<torch::Tensor> gorilla_decode(torch::Tensor blob,
   return {ts, vals};
 }
 
+// Phase A of the bucket aggregate on its own: the (slot, bucket) cell id of
+// every row, slot * n_buckets + bucket, or -1 where the row is filtered out.
+torch::Tensor bucket_cells(
+    torch::Tensor ts, torch::Tensor series, torch::Tensor slot_lut,
+    int64_t ts_lo, int64_t ts_hi, int64_t origin, int64_t bucket_ms,
+    int64_t n_buckets) {
+  CHECK_GPU(ts); CHECK_GPU(series); CHECK_GPU(slot_lut);
+  CHECK_CONTIG(ts); CHECK_CONTIG(series); CHECK_CONTIG(slot_lut);
+  TORCH_CHECK(ts.scalar_type() == torch::kInt64);
+  TORCH_CHECK(series.scalar_type() == torch::kInt32);
+  TORCH_CHECK(slot_lut.scalar_type() == torch::kInt32);
+  TORCH_CHECK(bucket_ms > 0 && n_buckets > 0 && n_buckets <= INT32_MAX);
+  const int64_t n = ts.numel();
+  TORCH_CHECK(series.numel() == n);
+  auto cell = torch::empty({n}, ts.options().dtype(torch::kInt32));
+  if (n == 0) return cell;
+  auto stream = at::cuda::getCurrentHIPStream().stream();
+  gdb_hip::launch_bucket_cells(
+      ts.data_ptr<int64_t>(), series.data_ptr<int32_t>(),
+      slot_lut.data_ptr<int32_t>(), (int)slot_lut.numel(), ts_lo, ts_hi,
+      origin, bucket_ms, (int)n_buckets, n, cell.data_ptr<int32_t>(), stream);
+  return cell;
+}
+
+// Exact grouped order statistics (K21). sources: (cell i32[n], fields
+// f64[nf_total, >=n] with unit inner stride, field_idx i32[nf]) triples that
+// accumulate into one state; selection s reads field row
+// field_idx[field_of_sel[s]] and looks for rank k1 = floor((cnt-1) * p[s]).
+// Returns (lo, hi f64[Q, n_cells], cnt i64[Q, n_cells]): the values of rank
+// k1 and min(k1+1, cnt-1) and the non-NaN count; NaN where cnt == 0.
+// field_of_sel is checked against field_idx's length here; the VALUES of
+// field_idx live on the device and are not read back: an entry outside
+// [0, fields.size(0)) makes the kernels skip that selection for that source
+// (its rows count nowhere, nothing out of bounds is touched). Callers build
+// field_idx on the host from valid row positions.
+// on_pass, if given, is called between the streaming passes (cancellation).
+// lds_cells caps the cell span a tile may have to count in LDS (the kernels
+// clamp it to their table size); 0 forces global atomics, for measurement.
+static constexpr int64_t kMaxQuantileCells = 262144;   // 256 MiB of u32 bins
+
+std::vector<torch::Tensor> grouped_quantile(
+    std::vector<std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>> sources,
+    std::vector<int64_t> field_of_sel, std::vector<double> p_of_sel,
+    int64_t n_cells, py::object on_pass, int64_t lds_cells) {
+  TORCH_CHECK(lds_cells >= 0, "lds_cells must not be negative");
+  const int64_t Q = (int64_t)field_of_sel.size();
+  TORCH_CHECK(Q >= 1, "grouped_quantile needs at least one selection");
+  TORCH_CHECK((int64_t)p_of_sel.size() == Q, "p_of_sel and field_of_sel differ in length");
+  TORCH_CHECK(n_cells >= 1, "n_cells must be positive");
+  TORCH_CHECK(n_cells <= kMaxQuantileCells && Q * n_cells <= kMaxQuantileCells,
+              "grouped_quantile: Q * n_cells = ", Q, " * ", n_cells,
+              " exceeds ", kMaxQuantileCells);
+  for (double p : p_of_sel)
+    TORCH_CHECK(p >= 0.0 && p <= 1.0, "p must lie in [0, 1], got ", p);
+  uint64_t total_rows = 0;
+  torch::Device dev(torch::kCPU);
+  for (auto& src : sources) {
+    auto& cell = std::get<0>(src);
+    auto& fields = std::get<1>(src);
+    auto& fidx = std::get<2>(src);
+    CHECK_GPU(cell); CHECK_GPU(fields); CHECK_GPU(fidx);
+    CHECK_CONTIG(cell); CHECK_CONTIG(fidx);
+    TORCH_CHECK(cell.scalar_type() == torch::kInt32 && cell.dim() == 1);
+    TORCH_CHECK(fidx.scalar_type() == torch::kInt32 && fidx.dim() == 1);
+    TORCH_CHECK(fields.scalar_type() == torch::kFloat64 && fields.dim() == 2);
+    TORCH_CHECK(fields.size(1) >= cell.numel(), "fields shorter than rows");
+    TORCH_CHECK(fields.size(1) <= 1 || fields.stride(1) == 1,
+                "fields must have unit stride along rows");
+    TORCH_CHECK(fields.size(0) <= 1 || fields.stride(0) >= fields.size(1),
+                "fields rows overlap");
+    for (int64_t f : field_of_sel)
+      TORCH_CHECK(f >= 0 && f < fidx.numel(), "field_of_sel ", f,
+                  " outside field_idx of length ", fidx.numel());
+    TORCH_CHECK(fields.device() == cell.device() && fidx.device() == cell.device(),
+                "a source's tensors must share one device");
+    TORCH_CHECK(std::get<0>(sources.front()).device() == cell.device(),
+                "all sources must be on the same device");
+    total_rows += (uint64_t)cell.numel();
+    dev = cell.device();
+  }
+  TORCH_CHECK(total_rows < (1ULL << 32),
+              "grouped_quantile: ", total_rows, " rows overflow the u32 bins");
+  const int64_t QC = Q * n_cells;
+  auto o_f64 = torch::TensorOptions().dtype(torch::kFloat64).device(dev);
+  auto o_i64 = torch::TensorOptions().dtype(torch::kInt64).device(dev);
+  auto cnt = torch::zeros({Q, n_cells}, o_i64);
+  if (total_rows == 0) {
+    auto nan = torch::full({Q, n_cells}, std::nan(""), o_f64);
+    return {nan, nan.clone(), cnt};
+  }
+  auto o_i32 = o_i64.dtype(torch::kInt32);
+  auto hist = torch::zeros({QC, 256}, o_i32);
+  auto prefix = torch::zeros({QC}, o_i64);
+  auto k_left = torch::zeros({QC}, o_i64);
+  auto k1 = torch::zeros({QC}, o_i64);
+  auto le = torch::zeros({QC}, o_i64);
+  auto next = torch::full({QC}, -1, o_i64);            // u64 max = "no next"
+  std::vector<int32_t> fos32(field_of_sel.begin(), field_of_sel.end());
+  auto fos = torch::from_blob(fos32.data(), {Q}, torch::kInt32).to(dev);
+  auto ps = torch::from_blob(p_of_sel.data(), {Q}, torch::kFloat64).to(dev);
+  auto stream = at::cuda::getCurrentHIPStream().stream();
+  auto* prefix_p = reinterpret_cast<unsigned long long*>(prefix.data_ptr<int64_t>());
+  auto* hist_p = reinterpret_cast<unsigned int*>(hist.data_ptr<int32_t>());
+  auto* le_p = reinterpret_cast<unsigned long long*>(le.data_ptr<int64_t>());
+  auto* next_p = reinterpret_cast<unsigned long long*>(next.data_ptr<int64_t>());
+  auto check = [](const char* what) {
+    const hipError_t err = hipGetLastError();
+    TORCH_CHECK(err == hipSuccess, what, " launch failed: ", hipGetErrorString(err));
+  };
+  auto between = [&]() { if (!on_pass.is_none()) on_pass(); };
+  auto field_stride = [](const torch::Tensor& f) {
+    return f.size(0) > 1 ? f.stride(0) : f.size(1);
+  };
+  for (int pass = 0; pass < 8; pass++) {
+    for (auto& src : sources) {
+      auto& cell = std::get<0>(src);
+      auto& fields = std::get<1>(src);
+      auto& fidx = std::get<2>(src);
+      if (cell.numel() == 0) continue;
+      gdb_hip::launch_quantile_hist(
+          cell.data_ptr<int32_t>(), fields.data_ptr<double>(), field_stride(fields),
+          fidx.data_ptr<int32_t>(), (int)fields.size(0), fos.data_ptr<int32_t>(),
+          (int)Q, cell.numel(), (int)n_cells, pass, (int)std::min<int64_t>(lds_cells, 1 << 20),
+          prefix_p, hist_p, stream);
+      check("quantile_hist");
+    }
+    gdb_hip::launch_quantile_pick(
+        hist_p, ps.data_ptr<double>(), (int)n_cells, QC, pass, prefix_p,
+        k_left.data_ptr<int64_t>(), k1.data_ptr<int64_t>(),
+        cnt.data_ptr<int64_t>(), stream);
+    check("quantile_pick");
+    between();
+  }
+  for (auto& src : sources) {
+    auto& cell = std::get<0>(src);
+    auto& fields = std::get<1>(src);
+    auto& fidx = std::get<2>(src);
+    if (cell.numel() == 0) continue;
+    gdb_hip::launch_quantile_next(
+        cell.data_ptr<int32_t>(), fields.data_ptr<double>(), field_stride(fields),
+        fidx.data_ptr<int32_t>(), (int)fields.size(0), fos.data_ptr<int32_t>(),
+        (int)Q, cell.numel(), (int)n_cells, (int)std::min<int64_t>(lds_cells, 1 << 20),
+        prefix_p, le_p, next_p, stream);
+    check("quantile_next");
+  }
+  auto lo = torch::empty({Q, n_cells}, o_f64);
+  auto hi = torch::empty({Q, n_cells}, o_f64);
+  gdb_hip::launch_quantile_finish(
+      prefix_p, k1.data_ptr<int64_t>(), cnt.data_ptr<int64_t>(), le_p, next_p,
+      QC, lo.data_ptr<double>(), hi.data_ptr<double>(), stream);
+  check("quantile_finish");
+  return {lo, hi, cnt};
+}
+
+// {tile rows, LDS cell capacity, grid cap} of the selection kernels.
+std::vector<int64_t> quantile_launch_config() {
+  int64_t c[3];
+  gdb_hip::quantile_launch_config(c);
+  return {c[0], c[1], c[2]};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ts_bucket_agg", &ts_bucket_agg, "fused filter + time-bucket aggregate",
         py::arg("ts"), py::arg("series"), py::arg("fields"), py::arg("field_idx"),
@@ -361,4 +543,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("scatter_append", &scatter_append, "bulk routed memtable append (K16)");
   m.def("scatter_append_packed", &scatter_append_packed,
         "K16 from one packed pinned block: one H2D copy + one launch");
+  m.def("bucket_cells", &bucket_cells, "(slot, bucket) cell id per row",
+        py::arg("ts"), py::arg("series"), py::arg("slot_lut"), py::arg("ts_lo"),
+        py::arg("ts_hi"), py::arg("origin"), py::arg("bucket_ms"),
+        py::arg("n_buckets"));
+  m.def("grouped_quantile", &grouped_quantile,
+        "exact grouped order statistics by radix-histogram selection (K21)",
+        py::arg("sources"), py::arg("field_of_sel"), py::arg("p_of_sel"),
+        py::arg("n_cells"), py::arg("on_pass") = py::none(),
+        py::arg("lds_cells") = 16);
+  m.def("quantile_launch_config", &quantile_launch_config,
+        "tile rows, LDS cell capacity and grid cap of the selection kernels");
 }

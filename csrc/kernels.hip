@@ -9,6 +9,8 @@
 //    over all selected fields.
 //  - filter_series_time_kernel : K1/K2 producing a keep-mask for raw scans.
 //  - dedup_mark_last_kernel : K4 last_row marker on (series, ts)-sorted data.
+//  - quantile_{hist,pick,next,finish}_kernel : K21 exact grouped order
+//    statistics by radix-histogram selection over bucket cells.
 //
 // Design notes (cdna_hip_programming.md):
 //  * 256-thread blocks (4 waves of 64), grid-stride, grid capped at
@@ -662,6 +664,273 @@ __global__ void prom_range_eval_kernel(
   }
 }
 
+// ------------------------------------- K21 grouped radix-histogram selection
+//
+// Exact order statistics per (selection, cell) with no sort: a selection is
+// a (field column, p) pair, a cell the (slot, bucket) id of the bucket-cell
+// pass. Eight rounds fix the sort key of rank k1 = floor((n-1)*p) one byte
+// at a time, most significant first: quantile_hist_kernel counts, per cell,
+// the keys that share the prefix fixed so far into 256 bins of the next
+// byte; quantile_pick_kernel walks the bins to the one holding the rank,
+// appends its byte to the prefix and clears the bins. quantile_next_kernel
+// then finds the rank's upper neighbour and quantile_finish_kernel decodes
+// both. Every streaming pass reads cell (4 B) + value (8 B) per row and
+// selection; the histogram is the only memory besides O(cells) state.
+//
+// Tile size and LDS span are a first choice, not a tuned one: 2048-row tiles
+// (8 rows per thread, cell ids held in registers across selections) and a
+// 16-cell x 256-bin u32 table = 16 KiB LDS, so four blocks per CU stay far
+// inside the 160 KiB; the grid is capped at 1024 blocks = 256 CUs x 4.
+// (series, ts)-sorted sources put a tile inside few cells; a tile that spans
+// more than 16 cells (unsorted input) counts through global atomics instead;
+// lds_cap (0..16) lowers that span at run time, 0 = global atomics only,
+// which is how the two paths are timed against each other.
+// Cell ids outside [0, n_cells) are skipped like -1.
+
+#define QSEL_TILE 2048
+#define QSEL_BLOCK 256
+#define QSEL_ROWS (QSEL_TILE / QSEL_BLOCK)
+#define QSEL_LDS_CELLS 16
+#define QSEL_MAX_GRID 1024
+
+// Loads the tile's cell ids into registers (-1 for rows past n or ids out of
+// range) and reduces their span through s_lo/s_hi. Returns false when no row
+// of the tile is kept. Every thread of the block must call it.
+DEV_INLINE bool qsel_load_tile(const int32_t* __restrict__ cell, int64_t t0,
+                               int64_t n, int n_cells, int32_t (&c)[QSEL_ROWS],
+                               int32_t* s_lo, int32_t* s_hi,
+                               int32_t& lo, int32_t& hi) {
+  const int tid = threadIdx.x;
+  if (tid == 0) { *s_lo = INT32_MAX; *s_hi = -1; }
+  __syncthreads();
+  int32_t my_lo = INT32_MAX, my_hi = -1;
+#pragma unroll
+  for (int j = 0; j < QSEL_ROWS; j++) {
+    const int64_t i = t0 + (int64_t)j * QSEL_BLOCK + tid;
+    int32_t v = -1;
+    if (i < n) {
+      v = cell[i];
+      if (v < 0 || v >= n_cells) v = -1;
+    }
+    c[j] = v;
+    if (v >= 0) { my_lo = min(my_lo, v); my_hi = max(my_hi, v); }
+  }
+  if (my_hi >= 0) {
+    atomicMin(s_lo, my_lo);
+    atomicMax(s_hi, my_hi);
+  }
+  __syncthreads();
+  lo = *s_lo;
+  hi = *s_hi;
+  __syncthreads();
+  return hi >= 0;
+}
+
+// hist: u32[Q, n_cells, 256]; prefix: u64[Q, n_cells]. pass 0..7, byte 0 is
+// the most significant key byte.
+__global__ void __launch_bounds__(QSEL_BLOCK) quantile_hist_kernel(
+    const int32_t* __restrict__ cell,
+    const double* __restrict__ fields, int64_t field_stride,
+    const int32_t* __restrict__ field_idx, int n_field_rows,
+    const int32_t* __restrict__ field_of_sel, int Q,
+    int64_t n, int n_cells, int pass, int lds_cap,
+    const unsigned long long* __restrict__ prefix,
+    unsigned int* __restrict__ hist) {
+  __shared__ int32_t s_lo, s_hi;
+  __shared__ unsigned int s_hist[QSEL_LDS_CELLS * 256];
+  __shared__ unsigned long long s_prefix[QSEL_LDS_CELLS];
+  const int tid = threadIdx.x;
+  const int hi_shift = 64 - 8 * pass;          // bits below the fixed prefix
+  const int byte_shift = 56 - 8 * pass;
+  const int64_t ntiles = (n + QSEL_TILE - 1) / QSEL_TILE;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t t0 = tile * QSEL_TILE;
+    int32_t c[QSEL_ROWS];
+    int32_t lo, hi;
+    if (!qsel_load_tile(cell, t0, n, n_cells, c, &s_lo, &s_hi, lo, hi)) continue;
+    const int range = hi - lo + 1;
+    const bool in_lds = range <= lds_cap;
+    for (int s = 0; s < Q; s++) {
+      const int32_t frow = field_idx[field_of_sel[s]];
+      if (frow < 0 || frow >= n_field_rows) continue;      // block-uniform
+      const double* __restrict__ col = fields + (int64_t)frow * field_stride;
+      const int64_t sbase = (int64_t)s * n_cells;
+      if (in_lds) {
+        for (int k = tid; k < range * 256; k += QSEL_BLOCK) s_hist[k] = 0u;
+        if (tid < range) s_prefix[tid] = prefix[sbase + lo + tid];
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < QSEL_ROWS; j++) {
+          if (c[j] < 0) continue;
+          const double v = col[t0 + (int64_t)j * QSEL_BLOCK + tid];
+          if (isnan(v)) continue;
+          const uint64_t key = f64_sort_key(v);
+          const int lc = c[j] - lo;
+          if (pass > 0 && (key >> hi_shift) != (s_prefix[lc] >> hi_shift)) continue;
+          atomicAdd(&s_hist[lc * 256 + (int)((key >> byte_shift) & 0xFF)], 1u);
+        }
+        __syncthreads();
+        for (int k = tid; k < range * 256; k += QSEL_BLOCK) {
+          const unsigned int h = s_hist[k];
+          if (h) atomicAdd(&hist[(sbase + lo) * 256 + k], h);
+        }
+        __syncthreads();
+      } else {
+#pragma unroll
+        for (int j = 0; j < QSEL_ROWS; j++) {
+          if (c[j] < 0) continue;
+          const double v = col[t0 + (int64_t)j * QSEL_BLOCK + tid];
+          if (isnan(v)) continue;
+          const uint64_t key = f64_sort_key(v);
+          const int64_t sc = sbase + c[j];
+          if (pass > 0 && (key >> hi_shift) != (prefix[sc] >> hi_shift)) continue;
+          atomicAdd(&hist[sc * 256 + (int)((key >> byte_shift) & 0xFF)], 1u);
+        }
+      }
+    }
+  }
+}
+
+// One wavefront per (selection, cell): lane l owns bins 4l..4l+3. Rows are
+// fewer than 2^32 per call (checked by the binding), so u32 sums cannot wrap.
+__global__ void __launch_bounds__(QSEL_BLOCK) quantile_pick_kernel(
+    unsigned int* __restrict__ hist,           // [QC, 256], cleared on exit
+    const double* __restrict__ p_of_sel, int n_cells, int64_t QC, int pass,
+    unsigned long long* __restrict__ prefix,   // [QC]
+    int64_t* __restrict__ k_left,              // [QC] rank still to find
+    int64_t* __restrict__ k1_out,              // [QC] rank of pass 0
+    int64_t* __restrict__ n_out) {             // [QC] non-NaN count
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = ((int64_t)blockIdx.x * QSEL_BLOCK + threadIdx.x) >> 6;
+  const int64_t nwaves = ((int64_t)gridDim.x * QSEL_BLOCK) >> 6;
+  for (int64_t idx = wave; idx < QC; idx += nwaves) {       // wave-uniform
+    if (pass > 0 && n_out[idx] == 0) continue;
+    uint4* bins4 = reinterpret_cast<uint4*>(hist + idx * 256) + lane;
+    const uint4 b = *bins4;
+    const unsigned int loc = b.x + b.y + b.z + b.w;
+    unsigned int incl = loc;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const unsigned int t = __shfl_up(incl, off, 64);
+      if (lane >= off) incl += t;
+    }
+    const unsigned int total = __shfl(incl, 63, 64);
+    int64_t k;
+    if (pass == 0) {
+      if (lane == 0) n_out[idx] = (int64_t)total;
+      if (total == 0) continue;                // empty cell: left alone
+      k = (int64_t)floor((double)((int64_t)total - 1) *
+                         p_of_sel[(int)(idx / n_cells)]);
+      if (lane == 0) k1_out[idx] = k;
+    } else {
+      k = k_left[idx];
+    }
+    const unsigned int excl = incl - loc;
+    if ((int64_t)excl <= k && k < (int64_t)incl) {           // exactly one lane
+      int64_t before = excl;
+      int d = 4 * lane;
+      if (k >= before + b.x) {
+        before += b.x; d++;
+        if (k >= before + b.y) {
+          before += b.y; d++;
+          if (k >= before + b.z) { before += b.z; d++; }
+        }
+      }
+      prefix[idx] |= (unsigned long long)d << (56 - 8 * pass);
+      k_left[idx] = k - before;
+    }
+    *bins4 = make_uint4(0u, 0u, 0u, 0u);
+  }
+}
+
+// le[s, cell] += (key <= prefix); next[s, cell] = min key > prefix (init ~0).
+__global__ void __launch_bounds__(QSEL_BLOCK) quantile_next_kernel(
+    const int32_t* __restrict__ cell,
+    const double* __restrict__ fields, int64_t field_stride,
+    const int32_t* __restrict__ field_idx, int n_field_rows,
+    const int32_t* __restrict__ field_of_sel, int Q,
+    int64_t n, int n_cells, int lds_cap,
+    const unsigned long long* __restrict__ prefix,
+    unsigned long long* __restrict__ le,
+    unsigned long long* __restrict__ next) {
+  __shared__ int32_t s_lo, s_hi;
+  __shared__ unsigned long long s_prefix[QSEL_LDS_CELLS];
+  __shared__ unsigned long long s_next[QSEL_LDS_CELLS];
+  __shared__ unsigned int s_le[QSEL_LDS_CELLS];
+  const int tid = threadIdx.x;
+  const int64_t ntiles = (n + QSEL_TILE - 1) / QSEL_TILE;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t t0 = tile * QSEL_TILE;
+    int32_t c[QSEL_ROWS];
+    int32_t lo, hi;
+    if (!qsel_load_tile(cell, t0, n, n_cells, c, &s_lo, &s_hi, lo, hi)) continue;
+    const int range = hi - lo + 1;
+    const bool in_lds = range <= lds_cap;
+    for (int s = 0; s < Q; s++) {
+      const int32_t frow = field_idx[field_of_sel[s]];
+      if (frow < 0 || frow >= n_field_rows) continue;      // block-uniform
+      const double* __restrict__ col = fields + (int64_t)frow * field_stride;
+      const int64_t sbase = (int64_t)s * n_cells;
+      if (in_lds) {
+        if (tid < range) {
+          s_prefix[tid] = prefix[sbase + lo + tid];
+          s_next[tid] = ~0ULL;
+          s_le[tid] = 0u;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < QSEL_ROWS; j++) {
+          if (c[j] < 0) continue;
+          const double v = col[t0 + (int64_t)j * QSEL_BLOCK + tid];
+          if (isnan(v)) continue;
+          const uint64_t key = f64_sort_key(v);
+          const int lc = c[j] - lo;
+          if (key <= s_prefix[lc]) atomicAdd(&s_le[lc], 1u);
+          else atomicMin(&s_next[lc], (unsigned long long)key);
+        }
+        __syncthreads();
+        if (tid < range) {
+          if (s_le[tid]) atomicAdd(&le[sbase + lo + tid], (unsigned long long)s_le[tid]);
+          if (s_next[tid] != ~0ULL) atomicMin(&next[sbase + lo + tid], s_next[tid]);
+        }
+        __syncthreads();
+      } else {
+#pragma unroll
+        for (int j = 0; j < QSEL_ROWS; j++) {
+          if (c[j] < 0) continue;
+          const double v = col[t0 + (int64_t)j * QSEL_BLOCK + tid];
+          if (isnan(v)) continue;
+          const uint64_t key = f64_sort_key(v);
+          const int64_t sc = sbase + c[j];
+          if (key <= prefix[sc]) atomicAdd(&le[sc], 1ULL);
+          else atomicMin(&next[sc], (unsigned long long)key);
+        }
+      }
+    }
+  }
+}
+
+// lo = value of rank k1, hi = value of rank min(k1+1, n-1); NaN where n == 0.
+__global__ void quantile_finish_kernel(
+    const unsigned long long* __restrict__ prefix,
+    const int64_t* __restrict__ k1, const int64_t* __restrict__ cnt,
+    const unsigned long long* __restrict__ le,
+    const unsigned long long* __restrict__ next,
+    int64_t QC, double* __restrict__ out_lo, double* __restrict__ out_hi) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < QC; i += stride) {
+    if (cnt[i] == 0) {
+      out_lo[i] = prom_nan();
+      out_hi[i] = prom_nan();
+      continue;
+    }
+    const double lo = sort_key_f64(prefix[i]);
+    const bool same = (k1[i] + 1 < (int64_t)le[i]) || next[i] == ~0ULL;
+    out_lo[i] = lo;
+    out_hi[i] = same ? lo : sort_key_f64(next[i]);
+  }
+}
+
 // ------------------------------------------------- K16 scatter append
 /// One launch appends a routed wire batch into MULTIPLE region memtables:
 // row i goes to region region_of[i] at row dst_off[i]. Replaces per-region
@@ -852,6 +1121,71 @@ void launch_series_last_row(
     unsigned long long* best_row, hipStream_t stream) {
   hipLaunchKernelGGL(series_last_row_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream,
       ts, series, slot_lut, lut_size, ts_lo, ts_hi, n, best_key, src_tag, best_row);
+}
+
+// phase A of K5 on its own: (slot, bucket) cell id per row, -1 = filtered out
+void launch_bucket_cells(
+    const int64_t* ts, const int32_t* series, const int32_t* slot_lut,
+    int lut_size, int64_t ts_lo, int64_t ts_hi, int64_t origin,
+    int64_t bucket_ms, int n_buckets, int64_t n, int32_t* cell,
+    hipStream_t stream) {
+  hipLaunchKernelGGL(bucket_cell_coalesced_kernel,
+      dim3(grid_for(n, 256)), dim3(256), 0, stream,
+      ts, series, slot_lut, lut_size, ts_lo, ts_hi, origin, bucket_ms,
+      n_buckets, n, cell);
+}
+
+static inline int qsel_grid(int64_t n) {
+  const int64_t ntiles = (n + QSEL_TILE - 1) / QSEL_TILE;
+  return (int)max(min(ntiles, (int64_t)QSEL_MAX_GRID), (int64_t)1);
+}
+
+void launch_quantile_hist(
+    const int32_t* cell, const double* fields, int64_t field_stride,
+    const int32_t* field_idx, int n_field_rows, const int32_t* field_of_sel,
+    int Q, int64_t n, int n_cells, int pass, int lds_cap,
+    const unsigned long long* prefix, unsigned int* hist, hipStream_t stream) {
+  lds_cap = min(lds_cap, QSEL_LDS_CELLS);
+  hipLaunchKernelGGL(quantile_hist_kernel, dim3(qsel_grid(n)), dim3(QSEL_BLOCK),
+      0, stream, cell, fields, field_stride, field_idx, n_field_rows,
+      field_of_sel, Q, n, n_cells, pass, lds_cap, prefix, hist);
+}
+
+void launch_quantile_pick(
+    unsigned int* hist, const double* p_of_sel, int n_cells, int64_t QC,
+    int pass, unsigned long long* prefix, int64_t* k_left, int64_t* k1,
+    int64_t* cnt, hipStream_t stream) {
+  const int64_t blocks = (QC + 3) / 4;           // 4 wavefronts per block
+  const int grid = (int)max(min(blocks, (int64_t)65536), (int64_t)1);
+  hipLaunchKernelGGL(quantile_pick_kernel, dim3(grid), dim3(QSEL_BLOCK), 0,
+      stream, hist, p_of_sel, n_cells, QC, pass, prefix, k_left, k1, cnt);
+}
+
+void launch_quantile_next(
+    const int32_t* cell, const double* fields, int64_t field_stride,
+    const int32_t* field_idx, int n_field_rows, const int32_t* field_of_sel,
+    int Q, int64_t n, int n_cells, int lds_cap, const unsigned long long* prefix,
+    unsigned long long* le, unsigned long long* next, hipStream_t stream) {
+  lds_cap = min(lds_cap, QSEL_LDS_CELLS);
+  hipLaunchKernelGGL(quantile_next_kernel, dim3(qsel_grid(n)), dim3(QSEL_BLOCK),
+      0, stream, cell, fields, field_stride, field_idx, n_field_rows,
+      field_of_sel, Q, n, n_cells, lds_cap, prefix, le, next);
+}
+
+void launch_quantile_finish(
+    const unsigned long long* prefix, const int64_t* k1, const int64_t* cnt,
+    const unsigned long long* le, const unsigned long long* next, int64_t QC,
+    double* out_lo, double* out_hi, hipStream_t stream) {
+  hipLaunchKernelGGL(quantile_finish_kernel, dim3(grid_for(QC, 256)), dim3(256),
+      0, stream, prefix, k1, cnt, le, next, QC, out_lo, out_hi);
+}
+
+// launch geometry of the selection kernels, for tests that size their inputs
+// to reach every path: {tile rows, LDS cell capacity, grid cap}
+void quantile_launch_config(int64_t out[3]) {
+  out[0] = QSEL_TILE;
+  out[1] = QSEL_LDS_CELLS;
+  out[2] = QSEL_MAX_GRID;
 }
 
 

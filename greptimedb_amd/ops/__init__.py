@@ -8,10 +8,13 @@ PyTorch/f64), which double as the numerics oracle for GPU tests.
 """
 
 from greptimedb_amd.ops.kernels import (  # noqa: F401
+    bucket_cells,
     dedup_mark_last,
     filter_series_time,
+    grouped_quantile,
     hip_ops_available,
     prom_range_eval,
+    quantile_lerp,
     series_last,
     ts_bucket_agg,
     ts_bucket_agg_acc,

@@ -56,6 +56,99 @@ def ts_bucket_agg(ts, series, fields, field_idx, slot_lut, ts_lo, ts_hi,
     return out_sum, out_cnt, out_min, out_max, out_rows
 
 
+def bucket_cells(ts, series, slot_lut, ts_lo, ts_hi, origin, bucket_ms,
+                 n_buckets):
+    """Cell id per row: slot * n_buckets + bucket as ts_bucket_agg assigns
+    it, -1 where the row is filtered out. Returns i32[n]."""
+    keep = (ts >= ts_lo) & (ts < ts_hi)
+    s = series.long().clamp(0, max(slot_lut.numel() - 1, 0))
+    in_lut = (series >= 0) & (series < slot_lut.numel())
+    slot = torch.where(in_lut, slot_lut[s].long() if slot_lut.numel()
+                       else torch.full_like(s, -1), torch.full_like(s, -1))
+    bucket = torch.div(ts - origin, bucket_ms, rounding_mode="floor")
+    keep &= (slot >= 0) & (bucket >= 0) & (bucket < n_buckets)
+    cell = slot * n_buckets + bucket
+    return torch.where(keep, cell, torch.full_like(cell, -1)).to(torch.int32)
+
+
+MAX_QUANTILE_CELLS = 262144   # Q * n_cells the device histogram allows
+
+
+def grouped_quantile(sources, field_of_sel, p_of_sel, n_cells, on_pass=None):
+    """Exact grouped order statistics. sources: [(cell i32[n], fields
+    f64[nf_total, >=n], field_idx i32[nf])] accumulate into one state;
+    selection s reads field row field_idx[field_of_sel[s]] with p_of_sel[s].
+    Returns (lo, hi f64[Q, n_cells], cnt i64[Q, n_cells]): per cell the
+    non-NaN count, the value of rank k1 = floor((cnt-1)*p) and of rank
+    min(k1+1, cnt-1); NaN where cnt == 0. Rows with cell < 0 are skipped."""
+    import numpy as np
+    Q = len(field_of_sel)
+    if Q < 1 or len(p_of_sel) != Q:
+        raise ValueError("grouped_quantile: one p per selection, at least one")
+    if n_cells < 1 or Q * n_cells > MAX_QUANTILE_CELLS:
+        raise RuntimeError(f"grouped_quantile: Q * n_cells = {Q} * {n_cells} "
+                           f"exceeds {MAX_QUANTILE_CELLS}")
+    if sum(int(c.numel()) for c, _f, _i in sources) >= 1 << 32:
+        raise RuntimeError("grouped_quantile: rows overflow the u32 bins")
+    lo = np.full((Q, n_cells), np.nan)
+    hi = np.full((Q, n_cells), np.nan)
+    cnt = np.zeros((Q, n_cells), dtype=np.int64)
+    for s in range(Q):
+        p = float(p_of_sel[s])
+        if not 0.0 <= p <= 1.0:
+            raise RuntimeError(f"p must lie in [0, 1], got {p}")
+        cells, vals = [], []
+        for cell, fields, fidx in sources:
+            m = int(cell.numel())
+            if m == 0:
+                continue
+            cells.append(cell.numpy())
+            vals.append(fields[int(fidx[field_of_sel[s]])][:m].numpy())
+        if not cells:
+            continue
+        c = np.concatenate(cells)
+        v = np.concatenate(vals)
+        ok = (c >= 0) & (c < n_cells) & ~np.isnan(v)
+        c, v = c[ok], v[ok]
+        order = np.argsort(c, kind="stable")
+        c, v = c[order], v[order]
+        ends = np.searchsorted(c, np.arange(n_cells), side="right")
+        start = 0
+        for ci in range(n_cells):
+            end = int(ends[ci])
+            if end > start:
+                a = np.sort(v[start:end])
+                m = end - start
+                k1 = int(np.floor((m - 1) * p))
+                cnt[s, ci] = m
+                lo[s, ci] = a[k1]
+                hi[s, ci] = a[min(k1 + 1, m - 1)]
+            start = end
+        if on_pass is not None:
+            on_pass()
+    return torch.from_numpy(lo), torch.from_numpy(hi), torch.from_numpy(cnt)
+
+
+def quantile_lerp(lo, hi, cnt, p):
+    """Final quantile from grouped_quantile's planes (numpy [Q, n_cells],
+    p: [Q]): linear interpolation between ranks k1 and k1+1 with weight
+    g = (cnt-1)*p - k1, in the two-sided form np.quantile uses so the result
+    equals np.quantile(values, p) bit for bit. NaN where cnt == 0."""
+    import numpy as np
+    lo = np.asarray(lo, dtype=np.float64)
+    hi = np.asarray(hi, dtype=np.float64)
+    cnt = np.asarray(cnt, dtype=np.int64)
+    pcol = np.asarray(p, dtype=np.float64).reshape(-1, *([1] * (lo.ndim - 1)))
+    virt = np.maximum(cnt - 1, 0).astype(np.float64) * pcol
+    g = virt - np.floor(virt)
+    with np.errstate(invalid="ignore"):
+        d = hi - lo
+        out = lo + d * g
+        upper = hi - d * (1.0 - g)
+    out = np.where(g >= 0.5, upper, out)
+    return np.where(cnt > 0, out, np.nan)
+
+
 def filter_series_time(ts, series, slot_lut, ts_lo, ts_hi):
     keep = (ts >= ts_lo) & (ts < ts_hi)
     if slot_lut is not None and slot_lut.numel() > 0:

@@ -72,6 +72,42 @@ def ts_bucket_agg(ts, series, fields, field_idx, slot_lut, ts_lo, ts_hi,
         bucket_ms, n_slots, n_buckets))
 
 
+def bucket_cells(ts, series, slot_lut, ts_lo, ts_hi, origin, bucket_ms,
+                 n_buckets):
+    """(slot, bucket) cell id per row, i32[n], -1 = filtered out: the first
+    phase of ts_bucket_agg on its own (see cpu_ref.bucket_cells)."""
+    if ts.is_cuda:
+        return _require_hip().bucket_cells(
+            ts, series, slot_lut, int(ts_lo), int(ts_hi), int(origin),
+            int(bucket_ms), int(n_buckets))
+    return cpu_ref.bucket_cells(ts, series, slot_lut, ts_lo, ts_hi, origin,
+                                bucket_ms, n_buckets)
+
+
+def grouped_quantile(sources, field_of_sel, p_of_sel, n_cells, on_pass=None,
+                     lds_cells=16):
+    """Exact grouped order statistics over [(cell, fields, field_idx)]
+    sources → (lo, hi, cnt), each [Q, n_cells] (see cpu_ref.grouped_quantile;
+    cpu_ref.quantile_lerp turns them into the final values). On GPU: eight
+    radix-histogram passes plus one neighbour pass, no sort and no host sync;
+    `on_pass` is called between passes. `lds_cells` (GPU only) caps the cell
+    span a row tile may have to count in LDS; 0 forces global atomics.
+    `field_idx` entries must be valid rows of `fields`: the GPU kernels skip
+    a selection whose entry is out of range instead of reading out of
+    bounds, they do not report it."""
+    sources = list(sources)
+    if sources and sources[0][0].is_cuda:
+        return tuple(_require_hip().grouped_quantile(
+            sources, [int(f) for f in field_of_sel],
+            [float(p) for p in p_of_sel], int(n_cells), on_pass,
+            int(lds_cells)))
+    return cpu_ref.grouped_quantile(sources, field_of_sel, p_of_sel, n_cells,
+                                    on_pass)
+
+
+quantile_lerp = cpu_ref.quantile_lerp
+
+
 def filter_series_time(ts, series, slot_lut, ts_lo, ts_hi):
     if ts.is_cuda:
         ops = _require_hip()

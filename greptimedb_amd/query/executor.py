@@ -71,6 +71,24 @@ class AggCall:
 
 
 @dataclass
+class _DeviceQuantilePlan:
+    """What _plan_device_quantile hands to _exec_device_quantile."""
+    sel: "ast.Select"          # the statement as written
+    sel2: "ast.Select"         # + hidden GROUP BY / ORDER BY projections
+    plan: "SelectPlan"         # plan of sel2
+    grid: tuple                # (ts_lo, ts_hi, origin, bucket_ms, n_buckets)
+    group_keys: dict
+    region_luts: list
+    n_slots: int
+    calls: list                # repr of each distinct percentile call
+    field_of_call: list        # its field column
+    p_of_sel: list             # its p
+    n_group: int               # hidden GROUP BY projections
+    order_desc: list           # DESC flag per hidden ORDER BY projection
+    null_fields: list          # fields with a hidden count() projection
+
+
+@dataclass
 class SelectPlan:
     table: TableState
     ts_lo: int | None
@@ -850,8 +868,9 @@ class Executor:
         import time as _time
         if not isinstance(e.stmt, ast.Select):
             raise PlanQuery("EXPLAIN supports SELECT")
+        dq = self._plan_device_quantile(e.stmt)
         try:
-            plan = self._plan_select(e.stmt)
+            plan = dq.plan if dq is not None else self._plan_select(e.stmt)
         except PlanQuery as pq:
             # general-shape fallback (expression aggregates, GROUP BY on
             # fields, ORDER BY expressions): materialize + derived eval
@@ -865,7 +884,10 @@ class Executor:
                              f"{(_time.perf_counter() - t0) * 1000:.3f} ms")
             return QueryResult(["plan"], [lines])
         lines = []
-        if any(_has_range_agg(x) for x, _a in e.stmt.projections):
+        if dq is not None:
+            path = (f"grouped-quantile (radix select, Q={len(dq.p_of_sel)}, "
+                    f"cells={dq.n_slots * dq.grid[4]})")
+        elif any(_has_range_agg(x) for x, _a in e.stmt.projections):
             path = "range-select (sliding-window kernel)"
         elif any(_collect_window_nodes(x, w := []) or w
                  for x, _a in e.stmt.projections):
@@ -1354,6 +1376,12 @@ class Executor:
             sel.having = self._resolve_subqueries(sel.having, sel)
         if isinstance(sel.table, str) and sel.table in self.engine.tables \
                 and self._has_sketch_agg(sel):
+            dq = self._plan_device_quantile(sel)
+            if dq is not None:
+                try:
+                    return self._exec_device_quantile(dq)
+                except PlanQuery:
+                    pass    # a shape the planner let through: host path
             return self._exec_sketch_select(sel)
         if sel.table is None:
             # constant select
@@ -1851,6 +1879,50 @@ class Executor:
                       {st.schema.time_index.name})
         needed: set = set()
 
+        # time-bucket calls (GROUP BY date_bin(...)) are not something the
+        # derived evaluator knows: lift each into a hidden "ts"-kind column
+        # computed from the time index, named after the call it replaces
+        ts_name = st.schema.time_index.name
+        buckets: dict = {}      # repr(call) -> (hidden column, BucketSpec)
+
+        def lift(e):
+            if isinstance(e, ast.Func) and e.name in BUCKET_FUNCS:
+                if repr(e) not in buckets:
+                    buckets[repr(e)] = (f"__bucket{len(buckets)}",
+                                        self._bucket_spec(e, ts_name))
+                return ast.Col(buckets[repr(e)][0])
+            if isinstance(e, ast.Func):
+                return ast.Func(e.name, [lift(a) for a in e.args], e.distinct)
+            if isinstance(e, ast.BinOp):
+                return ast.BinOp(e.op, lift(e.left), lift(e.right))
+            if isinstance(e, ast.UnaryOp):
+                return ast.UnaryOp(e.op, lift(e.operand))
+            return e
+
+        def has_bucket(e):
+            if isinstance(e, ast.Func):
+                return e.name in BUCKET_FUNCS or any(has_bucket(a) for a in e.args)
+            if isinstance(e, ast.BinOp):
+                return has_bucket(e.left) or has_bucket(e.right)
+            if isinstance(e, ast.UnaryOp):
+                return has_bucket(e.operand)
+            return False
+
+        if any(has_bucket(e) for e in
+               [e for e, _a in sel.projections] + list(sel.group_by) +
+               [e for e, _d in sel.order_by] +
+               ([sel.having] if sel.having is not None else [])):
+            from greptimedb_amd.query.derived import _name_of
+            sel = dataclasses.replace(
+                sel,
+                projections=[(lift(e), a or (_name_of(e, i) if has_bucket(e)
+                                             else None))
+                             for i, (e, a) in enumerate(sel.projections)],
+                group_by=[lift(g) for g in sel.group_by],
+                having=lift(sel.having) if sel.having is not None else None,
+                order_by=[(lift(e), d) for e, d in sel.order_by])
+            needed.add(ts_name)
+
         def collect(e):
             if isinstance(e, ast.Col) and e.name in table_cols:
                 needed.add(e.name)
@@ -1876,9 +1948,297 @@ class Executor:
             projections=[(ast.Col(c), None) for c in sorted(needed)],
             table=sel.table, table_alias=sel.table_alias, where=sel.where)
         base = self._exec_select(base_sel)
+        if buckets:
+            ts_col = np.asarray(base.columns[base.names.index(ts_name)],
+                                dtype=np.int64)
+            names, columns, kinds = (list(base.names), list(base.columns),
+                                     list(base.kinds))
+            for hidden, spec in buckets.values():
+                o = spec.origin or 0
+                names.append(hidden)
+                columns.append(o + (ts_col - o) // spec.bucket_ms * spec.bucket_ms)
+                kinds.append("ts")
+            base = QueryResult(names, columns, kinds)
         outer = dataclasses.replace(sel, table=None, table_alias=None,
                                     where=None)
         return select_over_result(outer, base)
+
+    # ------------------------------------------- device percentiles (K21)
+
+    # Class switch, like Ingestor._fused: False keeps approx_percentile /
+    # median on the materialising host path (_exec_sketch_select).
+    _device_quantile = True
+
+    def _plan_device_quantile(self, sel: ast.Select):
+        """Device plan for approx_percentile(field, p) / median(field)
+        grouped by tags and/or one time bucket, or None when the statement
+        has to stay on the host path. Nothing is scanned here."""
+        import dataclasses
+        from greptimedb_amd.ops.cpu_ref import MAX_QUANTILE_CELLS
+        if not self._device_quantile or self.dist is not None:
+            return None
+        if not (isinstance(sel.table, str) and sel.table in self.engine.tables
+                and self._has_sketch_agg(sel)):
+            return None
+        if sel.joins or sel.distinct or sel.ctes or sel.align_ms is not None:
+            return None
+        st = self.engine.table(sel.table)
+        float_fields = {c.name for c in st.schema.field_columns
+                        if c.dtype.is_float} & \
+            set(st.regions[0].field_names)
+
+        sels: dict[str, tuple[str, float]] = {}   # repr(call) -> (field, p)
+        agg_args: set = set()      # fields under sum/avg/min/max
+
+        def walk(e, in_agg):
+            """False as soon as the expression leaves the supported shape."""
+            if isinstance(e, (ast.Lit, ast.Col, ast.Star, ast.Interval)):
+                return True
+            if isinstance(e, ast.BinOp):
+                return walk(e.left, in_agg) and walk(e.right, in_agg)
+            if isinstance(e, ast.UnaryOp):
+                return walk(e.operand, in_agg)
+            if not isinstance(e, ast.Func):
+                return False
+            fn = e.name.lower()
+            if fn in self._SKETCH_AGGS:
+                if in_agg or e.distinct or fn not in ("approx_percentile", "median"):
+                    return False
+                if len(e.args) != (2 if fn == "approx_percentile" else 1):
+                    return False
+                col = e.args[0]
+                if not (isinstance(col, ast.Col) and col.name in float_fields):
+                    return False
+                p = 0.5
+                if fn == "approx_percentile":
+                    try:
+                        p = _eval_const(e.args[1])
+                    except Exception:
+                        return False
+                    if isinstance(p, bool) or not isinstance(p, (int, float)):
+                        return False
+                    p = float(p)
+                    if not 0.0 <= p <= 1.0:
+                        return False
+                sels[repr(e)] = (col.name, p)
+                return True
+            if e.name in AGG_FUNCS and e.name != "count" and e.args and \
+                    isinstance(e.args[0], ast.Col):
+                agg_args.add(e.args[0].name)
+            nested = in_agg or e.name in AGG_FUNCS
+            return all(walk(a, nested) for a in e.args)
+
+        def positional(e):
+            if isinstance(e, ast.Lit) and isinstance(e.value, int) and \
+                    not isinstance(e.value, bool) and \
+                    1 <= e.value <= len(sel.projections):
+                return sel.projections[e.value - 1][0]
+            return e
+
+        group_by = [positional(g) for g in sel.group_by]
+        order_by = [(positional(e), d) for e, d in sel.order_by]
+        if any(isinstance(e, ast.Star) for e, _a in sel.projections):
+            return None
+        exprs = [e for e, _a in sel.projections] + [e for e, _d in order_by]
+        if sel.having is not None:
+            exprs.append(sel.having)
+        if not all(walk(e, False) for e in exprs) or not sels:
+            return None
+        if any(_has_range_agg(e) for e in exprs) or \
+                any(_collect_window_nodes(e, w := []) or w for e in exprs):
+            return None
+        # GROUP BY keys and ORDER BY expressions ride along as hidden
+        # projections: _plan_select then collects their aggregates, and the
+        # result is ordered afterwards the way the host path orders it. One
+        # hidden count(field) per aggregated field tells NULL (no value in
+        # the group) from a NaN that the arithmetic produced.
+        null_fields = sorted({f for f, _p in sels.values()} | agg_args)
+        hidden = [(g, None) for g in group_by] + \
+            [(e, None) for e, _d in order_by] + \
+            [(ast.Func("count", [ast.Col(f)]), None) for f in null_fields]
+        sel2 = dataclasses.replace(
+            sel, projections=list(sel.projections) + hidden, group_by=group_by,
+            order_by=[], limit=None, offset=None)
+        try:
+            plan = self._plan_select(sel2)
+            if any(a.func in ("last_value", "first_value", "count_distinct")
+                   for a in plan.aggs):
+                return None
+            grid = self._agg_time_grid(plan)
+        except PlanQuery:
+            return None
+        # ordinary aggregates read the f64 field matrix: anything else
+        # (count(ts), max(tag), an unknown column) stays on the host path
+        numeric = set(st.regions[0].field_names)
+        if any(a.arg is not None and a.arg not in numeric for a in plan.aggs):
+            return None
+        aliases = {a for _e, a in sel.projections if a}
+
+        def finalizable(e):
+            """What _finalize_agg can evaluate over group rows."""
+            if isinstance(e, ast.Lit):
+                return True
+            if isinstance(e, ast.Col):
+                return e.name in aliases or e.name in plan.group_tags
+            if isinstance(e, ast.BinOp):
+                return finalizable(e.left) and finalizable(e.right)
+            if isinstance(e, ast.UnaryOp):
+                return finalizable(e.operand)
+            if isinstance(e, ast.Func):
+                return repr(e) in sels or e.name in AGG_FUNCS or (
+                    plan.bucket_expr is not None and
+                    _same_expr(e, plan.bucket_expr))
+            return False
+        if not all(finalizable(e) for e in exprs):
+            return None
+        group_keys, region_luts = self._build_group_luts(st, plan, plan.group_tags)
+        n_slots = max(len(group_keys), 1)
+        calls = list(sels)
+        if len(calls) * n_slots * grid[4] > MAX_QUANTILE_CELLS:
+            return None
+        return _DeviceQuantilePlan(
+            sel=sel, sel2=sel2, plan=plan, grid=grid, group_keys=group_keys,
+            region_luts=region_luts, n_slots=n_slots, calls=calls,
+            field_of_call=[sels[c][0] for c in calls],
+            p_of_sel=[sels[c][1] for c in calls],
+            n_group=len(group_by), order_desc=[d for _e, d in order_by],
+            null_fields=null_fields)
+
+    def _exec_device_quantile(self, dq) -> QueryResult:
+        """Percentiles where the data lives: per source one bucket-cell pass
+        feeds both the fused aggregate (ordinary aggregates, row counts) and
+        the radix-histogram selection; only [Q, cells] planes reach the host.
+        Output mirrors _exec_sketch_select: names, kinds, float-or-None
+        values, rows ordered by group key unless ORDER BY says otherwise."""
+        from greptimedb_amd.ops import (bucket_cells, grouped_quantile,
+                                        quantile_lerp, ts_bucket_agg_acc,
+                                        ts_bucket_agg_finish)
+        from greptimedb_amd.query.derived import _contains_agg, _name_of
+        plan, sel = dq.plan, dq.sel
+        st = plan.table
+        device = self.engine.config.device
+        ts_lo, ts_hi, origin, bucket_ms, n_buckets = dq.grid
+        n_slots = dq.n_slots
+        agg_fields = sorted({a.arg for a in plan.aggs if a.arg is not None} |
+                            set(dq.field_of_call))
+        nf = len(agg_fields)
+        field_of_sel = [agg_fields.index(f) for f in dq.field_of_call]
+
+        # The cell ids (4 B per row) and, for merge-mode or residual-filtered
+        # regions, the deduplicated field copies of every source stay alive
+        # across the nine passes, next to the histogram.
+        acc = None
+        sources = []
+        for region, lut in zip(st.regions, dq.region_luts):
+            self._cancel_check()
+            lut_t = torch.as_tensor(lut, device=device)
+            for ts_t, se_t, f_t, fidx_t in self._region_agg_inputs(
+                    region, plan, device, agg_fields, ts_lo, ts_hi):
+                acc = ts_bucket_agg_acc(ts_t, se_t, f_t, fidx_t, lut_t,
+                                        ts_lo, ts_hi, origin, bucket_ms,
+                                        n_slots, n_buckets, acc=acc)
+                cell = bucket_cells(ts_t, se_t, lut_t, ts_lo, ts_hi, origin,
+                                    bucket_ms, n_buckets)
+                sources.append((cell, f_t, fidx_t))
+        self._cancel_check()
+        shape = (n_slots, n_buckets)
+        if acc is None:
+            sums = np.zeros((nf,) + shape)
+            cnts = np.zeros((nf,) + shape, dtype=np.int64)
+            mins = np.full((nf,) + shape, np.nan)
+            maxs = np.full((nf,) + shape, np.nan)
+            rowcnt = np.zeros(shape, dtype=np.int64)
+            qvals = np.full((len(dq.calls),) + shape, np.nan)
+        else:
+            lo, hi, cnt = grouped_quantile(
+                sources, field_of_sel, dq.p_of_sel, n_slots * n_buckets,
+                on_pass=self._cancel_check)
+            sums, cnts, mins, maxs, rowcnt = [
+                t.cpu().numpy() for t in ts_bucket_agg_finish(acc)]
+            qvals = quantile_lerp(lo.cpu().numpy(), hi.cpu().numpy(),
+                                  cnt.cpu().numpy(), dq.p_of_sel)
+            qvals = qvals.reshape((len(dq.calls),) + shape)
+        del sources
+        plane_of = {c: qvals[i] for i, c in enumerate(dq.calls)}
+        field_of = dict(zip(dq.calls, dq.field_of_call))
+
+        res = self._finalize_agg(
+            dq.sel2, plan, dq.group_keys, origin, bucket_ms, agg_fields,
+            sums, cnts, mins, maxs, rowcnt,
+            extra_planes=lambda e: plane_of.get(repr(e)))
+
+        # order, cut and format the way the host path does
+        n_vis = len(sel.projections)
+        n_ord = len(dq.order_desc)
+        cols = [np.asarray(c) for c in res.columns]
+        m = len(cols[0]) if cols else 0
+        gcols = cols[n_vis:n_vis + dq.n_group]
+        o0 = n_vis + dq.n_group
+        cnt_of = dict(zip(dq.null_fields, cols[o0 + n_ord:]))
+        alias_expr = {a: e for e, a in sel.projections if a}
+
+        def null_mask(e):
+            """Rows where the host path yields None: an aggregate over a
+            group without a non-NULL value, or arithmetic on one."""
+            if isinstance(e, ast.Lit):
+                return np.full(m, e.value is None)
+            if isinstance(e, ast.Col) and e.name in alias_expr:
+                return null_mask(alias_expr[e.name])
+            if isinstance(e, ast.BinOp):
+                return null_mask(e.left) | null_mask(e.right)
+            if isinstance(e, ast.UnaryOp):
+                return null_mask(e.operand)
+            if isinstance(e, ast.Func) and repr(e) in field_of:
+                return cnt_of[field_of[repr(e)]] == 0
+            if isinstance(e, ast.Func) and e.name in AGG_FUNCS and \
+                    e.name != "count" and isinstance(e.args[0], ast.Col):
+                return cnt_of[e.args[0].name] == 0
+            return np.zeros(m, dtype=bool)
+
+        def rank(col, e, desc=False):
+            """Sort codes of one key column: value order, NULL/NaN last
+            (first when descending), as derived._sort_key orders them."""
+            if col.dtype == object:
+                null = np.array([v is None for v in col], dtype=bool)
+            else:
+                null = np.isnan(col) if col.dtype.kind == "f" else \
+                    np.zeros(m, dtype=bool)
+            null = null | null_mask(e)
+            code = np.zeros(m, dtype=np.int64)
+            if not null.all():
+                _u, inv = np.unique(col[~null], return_inverse=True)
+                code[~null] = inv
+                code[null] = int(inv.max()) + 1
+            return -code if desc else code
+
+        hidden = dq.sel2.projections
+        idx = np.arange(m)
+        if gcols and m:
+            idx = np.lexsort(tuple(
+                rank(g, hidden[n_vis + i][0])
+                for i, g in reversed(list(enumerate(gcols)))))
+        if n_ord and m:
+            keys = [rank(cols[o0 + i], hidden[o0 + i][0], dq.order_desc[i])[idx]
+                    for i in range(n_ord)]
+            idx = idx[np.lexsort(tuple(reversed(keys)))]
+        if sel.offset:
+            idx = idx[sel.offset:]
+        if sel.limit is not None:
+            idx = idx[: sel.limit]
+        names, out, kinds = [], [], []
+        for pi, (e, a) in enumerate(sel.projections):
+            names.append(a or _name_of(e, pi))
+            kinds.append(res.kinds[pi])
+            if _contains_agg(e):
+                vals = cols[pi].astype(np.float64)[idx]
+                null = null_mask(e)[idx]
+                if null.any():
+                    vals = vals.astype(object)
+                    vals[null] = None
+                out.append(list(vals))
+            else:
+                out.append(list(cols[pi][idx]))
+        return QueryResult(names, out, kinds)
 
     def _with_ctes(self, stmt):
 
@@ -2116,13 +2476,11 @@ class Executor:
             region_luts.append(lut)
         return group_keys, region_luts
 
-    def _exec_aggregate(self, sel: ast.Select, plan: SelectPlan) -> QueryResult:
-        if any(a.func in ("last_value", "first_value") for a in plan.aggs):
-            return self._exec_lastpoint(sel, plan)
+    def _agg_time_grid(self, plan: SelectPlan):
+        """(ts_lo, ts_hi, origin, bucket_ms, n_buckets) of an aggregate
+        plan: open time bounds close on the regions' data range, the bucket
+        grid starts at the bucket holding ts_lo."""
         st = plan.table
-        device = self.engine.config.device
-
-        # time bounds
         ts_lo, ts_hi = plan.ts_lo, plan.ts_hi
         if ts_lo is None or ts_hi is None:
             lo = hi = None
@@ -2153,6 +2511,15 @@ class Executor:
             bucket_ms = max(int(ts_hi - ts_lo), 1)
             origin = ts_lo
             n_buckets = 1
+        return ts_lo, ts_hi, origin, bucket_ms, n_buckets
+
+    def _exec_aggregate(self, sel: ast.Select, plan: SelectPlan) -> QueryResult:
+        if any(a.func in ("last_value", "first_value") for a in plan.aggs):
+            return self._exec_lastpoint(sel, plan)
+        st = plan.table
+        device = self.engine.config.device
+
+        ts_lo, ts_hi, origin, bucket_ms, n_buckets = self._agg_time_grid(plan)
 
         # count(DISTINCT tag): group by (outer tags + distinct tag) internally,
         # then collapse effective groups back to outer groups at finalize
@@ -2436,7 +2803,11 @@ class Executor:
 
     def _finalize_agg(self, sel, plan, group_keys, origin, bucket_ms,
                       agg_fields, sums, cnts, mins, maxs, rowcnt,
-                      distinct_plane=None, dtag=None) -> QueryResult:
+                      distinct_plane=None, dtag=None,
+                      extra_planes=None) -> QueryResult:
+        """`extra_planes(func_expr)`, when given, may resolve a function
+        call the fused aggregates do not know (a percentile) to its
+        [n_slots, n_buckets] plane; it returns None for any other call."""
         # cells with data
         slot_idx, bucket_idx = np.nonzero(rowcnt)
         if len(slot_idx) == 0 and not plan.group_tags and plan.bucket is None:
@@ -2496,6 +2867,10 @@ class Executor:
             if isinstance(e, ast.Func):
                 if plan.bucket_expr is not None and _same_expr(e, plan.bucket_expr):
                     return bucket_ts, "ts"
+                if extra_planes is not None:
+                    plane = extra_planes(e)
+                    if plane is not None:
+                        return plane[slot_idx, bucket_idx], ""
                 if e.name in AGG_FUNCS:
                     if len(e.args) == 1 and isinstance(e.args[0], ast.Star):
                         return agg_array("count", None), ""
@@ -3938,3 +4313,6 @@ def _expr_name(e: ast.Expr) -> str:
     if isinstance(e, ast.Cast):
         return f"CAST({_expr_name(e.expr)} AS {e.type.upper()})"
     return repr(e)
+
+
+QueryExecutor = Executor
