@@ -325,12 +325,20 @@ void scatter_append_packed(
                 "row ", i, ": destination row beyond region ", r, " capacity");
   }
   auto stream = at::cuda::getCurrentHIPStream().stream();
-  const hipError_t err = hipMemcpyAsync(
-      stage_dev.data_ptr<uint8_t>(), hp, (size_t)used, hipMemcpyHostToDevice, stream);
+  uint8_t* dp = stage_dev.data_ptr<uint8_t>();
+  // Everything above ran under the GIL; from here on only raw pointers and
+  // plain values are touched, so the copy and the launch are queued with the
+  // GIL released: other ingest workers run their Python sections meanwhile.
+  hipError_t err = hipSuccess, lerr = hipSuccess;
+  {
+    py::gil_scoped_release nogil;
+    err = hipMemcpyAsync(dp, hp, (size_t)used, hipMemcpyHostToDevice, stream);
+    if (err == hipSuccess) {
+      gdb_hip::launch_scatter_append_packed(dp, n, (int)nf, regs, stream);
+      lerr = hipGetLastError();
+    }
+  }
   TORCH_CHECK(err == hipSuccess, "stage upload failed: ", hipGetErrorString(err));
-  gdb_hip::launch_scatter_append_packed(
-      stage_dev.data_ptr<uint8_t>(), n, (int)nf, regs, stream);
-  const hipError_t lerr = hipGetLastError();
   TORCH_CHECK(lerr == hipSuccess, "scatter_append_packed launch failed: ",
               hipGetErrorString(lerr));
 }

@@ -8,6 +8,7 @@
 //  2. WalWriter — segmented group-commit WAL writer (reference:
 //     src/log-store raft_engine backend + mito2 wal.rs:187 WalWriter).
 //     Frame: [u32 len][u32 crc32][u64 region_id][u64 seq][payload].
+//     Frame, checksum and file logic live in csrc/wal_core.h.
 //
 // Deliberately torch-free: compiles in seconds, usable from any process.
 
@@ -27,42 +28,13 @@
 #include <vector>
 
 #include "ingest_core.h"
+#include "wal_core.h"
 
 namespace py = pybind11;
 
-// ------------------------------------- crc32 (IEEE, zlib-compatible, slice-by-8)
-static uint32_t crc_table[8][256];
-static bool crc_init_done = [] {
-  for (uint32_t i = 0; i < 256; i++) {
-    uint32_t c = i;
-    for (int k = 0; k < 8; k++) c = (c & 1) ? 0xEDB88320u ^ (c >> 1) : c >> 1;
-    crc_table[0][i] = c;
-  }
-  for (int t = 1; t < 8; t++)
-    for (uint32_t i = 0; i < 256; i++)
-      crc_table[t][i] = crc_table[0][crc_table[t - 1][i] & 0xFF] ^
-                        (crc_table[t - 1][i] >> 8);
-  return true;
-}();
-
-static uint32_t crc32_update(uint32_t crc, const uint8_t* buf, size_t len) {
-  crc = ~crc;
-  while (len >= 8) {
-    uint32_t lo, hi;
-    std::memcpy(&lo, buf, 4);
-    std::memcpy(&hi, buf + 4, 4);
-    lo ^= crc;
-    crc = crc_table[7][lo & 0xFF] ^ crc_table[6][(lo >> 8) & 0xFF] ^
-          crc_table[5][(lo >> 16) & 0xFF] ^ crc_table[4][lo >> 24] ^
-          crc_table[3][hi & 0xFF] ^ crc_table[2][(hi >> 8) & 0xFF] ^
-          crc_table[1][(hi >> 16) & 0xFF] ^ crc_table[0][hi >> 24];
-    buf += 8;
-    len -= 8;
-  }
-  for (size_t i = 0; i < len; i++)
-    crc = crc_table[0][(crc ^ buf[i]) & 0xFF] ^ (crc >> 8);
-  return ~crc;
-}
+// crc32 (IEEE, zlib-compatible): csrc/wal_core.h, carry-less-multiply
+// folding where the CPU has it, slice-by-8 otherwise and for tails.
+using gdb_wal::crc32_update;
 
 // FNV-1a 64-bit over a byte range (interning probe of the prom/otlp parsers
 // and the tokenizer; the line parser hashes a word at a time, ingest_core.h).
@@ -248,129 +220,133 @@ class LineParser {
 
 
 // ---------------------------------------------------------------- WalWriter
+// pybind glue over gdb_wal::WalWriter (csrc/wal_core.h). The writer is
+// internally synchronized, so every call below runs its native part without
+// the GIL.
 
-class WalWriter {
- public:
-  WalWriter() = default;
-  ~WalWriter() { close_segment(); }
+// A payload argument: bytes or any contiguous buffer (the fused ingest path
+// hands over uint8 views of its payload arena). Acquire and release under
+// the GIL.
+struct PayloadView {
+  const uint8_t* p = nullptr;
+  size_t n = 0;
+  Py_buffer view;
+  bool have_view = false;
+  py::object owner;   // keeps a bytes payload alive while the GIL is released
 
-  void open_segment(const std::string& path) {
-    close_segment();
-    fd_ = ::open(path.c_str(), O_CREAT | O_WRONLY | O_APPEND, 0644);
-    if (fd_ < 0) throw std::runtime_error("wal open failed: " + path + ": " + strerror(errno));
-    path_ = path;
-    seg_bytes_ = ::lseek(fd_, 0, SEEK_END);
-  }
+  PayloadView() = default;
+  PayloadView(const PayloadView&) = delete;
+  PayloadView& operator=(const PayloadView&) = delete;
+  ~PayloadView() { if (have_view) PyBuffer_Release(&view); }
 
-  void close_segment() {
-    if (fd_ >= 0) { ::close(fd_); fd_ = -1; }
-  }
-
-  // Buffer one entry (group commit happens in commit()). The crc over the
-  // payload runs without the GIL — it is the ingest path's biggest
-  // GIL-held C++ cost otherwise (callers serialize via the python Wal lock).
-  // `payload` is bytes or any contiguous buffer (the fused ingest path hands
-  // over uint8 views of its payload arena).
-  void append(uint64_t region_id, uint64_t seq, py::object payload) {
-    char* pbuf; Py_ssize_t plen;
-    Py_buffer view;
-    bool have_view = false;
-    if (PyBytes_Check(payload.ptr())) {
-      if (PyBytes_AsStringAndSize(payload.ptr(), &pbuf, &plen) != 0)
+  void acquire(PyObject* o) {
+    owner = py::reinterpret_borrow<py::object>(o);
+    if (PyBytes_Check(o)) {
+      char* b; Py_ssize_t len;
+      if (PyBytes_AsStringAndSize(o, &b, &len) != 0)
         throw std::runtime_error("payload must be bytes");
+      p = reinterpret_cast<const uint8_t*>(b);
+      n = (size_t)len;
     } else {
-      if (PyObject_GetBuffer(payload.ptr(), &view, PyBUF_SIMPLE) != 0)
+      if (PyObject_GetBuffer(o, &view, PyBUF_SIMPLE) != 0)
         throw py::error_already_set();
       have_view = true;
-      pbuf = static_cast<char*>(view.buf);
-      plen = view.len;
+      p = static_cast<const uint8_t*>(view.buf);
+      n = (size_t)view.len;
     }
-    struct Release {
-      Py_buffer* v;
-      ~Release() { if (v) PyBuffer_Release(v); }
-    } release{have_view ? &view : nullptr};
-    py::gil_scoped_release rel;
-    uint32_t body_len = 16 + static_cast<uint32_t>(plen);
-    size_t off = buf_.size();
-    buf_.resize(off + 8 + body_len);
-    uint8_t* w = buf_.data() + off;
-    std::memcpy(w, &body_len, 4);
-    // crc over [region][seq][payload]
-    uint8_t hdr[16];
-    std::memcpy(hdr, &region_id, 8);
-    std::memcpy(hdr + 8, &seq, 8);
-    uint32_t crc = crc32_update(0, hdr, 16);
-    crc = crc32_update(crc, reinterpret_cast<uint8_t*>(pbuf), plen);
-    std::memcpy(w + 4, &crc, 4);
-    std::memcpy(w + 8, hdr, 16);
-    std::memcpy(w + 24, pbuf, plen);
   }
-
-  // Flush buffered entries; optionally fdatasync. Returns segment size.
-  uint64_t commit(bool sync) {
-    if (fd_ < 0) throw std::runtime_error("wal: no open segment");
-    size_t n = buf_.size();
-    if (n) {
-      py::gil_scoped_release rel;
-      const uint8_t* p = buf_.data();
-      size_t left = n;
-      while (left) {
-        ssize_t w = ::write(fd_, p, left);
-        if (w < 0) {
-          if (errno == EINTR) continue;
-          throw std::runtime_error(std::string("wal write failed: ") + strerror(errno));
-        }
-        p += w; left -= w;
-      }
-      if (sync && ::fdatasync(fd_) != 0)
-        throw std::runtime_error(std::string("wal fdatasync failed: ") + strerror(errno));
-    }
-    buf_.clear();
-    seg_bytes_ += n;
-    return seg_bytes_;
-  }
-
-  uint64_t segment_bytes() const { return seg_bytes_; }
-
- private:
-  int fd_ = -1;
-  std::string path_;
-  uint64_t seg_bytes_ = 0;
-  std::vector<uint8_t> buf_;
 };
+
+// Buffer one entry (group commit happens in commit()). Checksum and copy
+// run without the GIL.
+static void wal_writer_append(gdb_wal::WalWriter& w, uint64_t region_id,
+                              uint64_t seq, py::object payload) {
+  PayloadView v;
+  v.acquire(payload.ptr());
+  py::gil_scoped_release rel;
+  w.append(region_id, seq, v.p, v.n);
+}
+
+// Write one frame per entry straight through to its writer's segment:
+// entry i is (writers[i], region_ids[i], seqs[i], payloads[i]); a writer may
+// appear more than once. All buffer views are taken first, then the GIL is
+// released once for the whole call: every checksum is computed before any
+// writer's mutex is taken, and each frame is written with writev from the
+// caller's buffer (after whatever the writer still had buffered). With
+// `sync`, each writer is fdatasync'ed once, after its last frame. Returns
+// the segment size of each entry's writer after its frame.
+static py::list wal_append_commit(py::list writers,
+                                  std::vector<uint64_t> region_ids,
+                                  std::vector<uint64_t> seqs,
+                                  py::list payloads, bool sync) {
+  const size_t m = (size_t)py::len(writers);
+  if (region_ids.size() != m || seqs.size() != m || (size_t)py::len(payloads) != m)
+    throw std::runtime_error("wal_append_commit: argument lists differ in length");
+  std::vector<gdb_wal::WalWriter*> w(m);
+  std::vector<py::object> writer_refs(m);
+  std::vector<PayloadView> views(m);
+  for (size_t i = 0; i < m; i++) {
+    writer_refs[i] = writers[i];
+    w[i] = py::cast<gdb_wal::WalWriter*>(writer_refs[i]);
+    if (w[i] == nullptr)
+      throw std::runtime_error("wal_append_commit: writer is None");
+    views[i].acquire(py::object(payloads[i]).ptr());
+  }
+  std::vector<uint64_t> sizes(m, 0);
+  std::string error;
+  {
+    py::gil_scoped_release rel;
+    try {
+      std::vector<uint8_t> hdrs(m * gdb_wal::kFrameHeaderBytes);
+      for (size_t i = 0; i < m; i++)
+        gdb_wal::frame_header(hdrs.data() + i * gdb_wal::kFrameHeaderBytes,
+                              region_ids[i], seqs[i], views[i].p, views[i].n);
+      for (size_t i = 0; i < m; i++) {
+        bool last_of_writer = true;
+        for (size_t j = i + 1; j < m && last_of_writer; j++)
+          last_of_writer = w[j] != w[i];
+        sizes[i] = w[i]->append_commit(
+            hdrs.data() + i * gdb_wal::kFrameHeaderBytes, views[i].p,
+            views[i].n, sync && last_of_writer);
+      }
+    } catch (const std::exception& e) {
+      error = e.what();
+      if (error.empty()) error = "wal_append_commit failed";
+    }
+  }
+  if (!error.empty()) throw std::runtime_error(error);
+  py::list out;
+  for (size_t i = 0; i < m; i++) out.append(py::int_(sizes[i]));
+  return out;
+}
 
 // Read back one WAL segment: returns list of (region_id, seq, payload bytes).
 // Stops at the first corrupt/truncated frame (torn tail after crash).
 static py::list wal_read_segment(const std::string& path) {
+  std::vector<uint8_t> data;
+  std::vector<gdb_wal::FrameView> frames;
+  {
+    py::gil_scoped_release rel;
+    data = gdb_wal::read_file(path);
+    frames = gdb_wal::read_frames(data.data(), data.size());
+  }
   py::list out;
-  int fd = ::open(path.c_str(), O_RDONLY);
-  if (fd < 0) throw std::runtime_error("wal open failed: " + path);
-  off_t sz = ::lseek(fd, 0, SEEK_END);
-  ::lseek(fd, 0, SEEK_SET);
-  std::vector<uint8_t> data(sz);
-  size_t got = 0;
-  while (got < static_cast<size_t>(sz)) {
-    ssize_t r = ::read(fd, data.data() + got, sz - got);
-    if (r <= 0) break;
-    got += r;
-  }
-  ::close(fd);
-  size_t off = 0;
-  while (off + 8 <= got) {
-    uint32_t body_len, crc;
-    std::memcpy(&body_len, data.data() + off, 4);
-    std::memcpy(&crc, data.data() + off + 4, 4);
-    if (body_len < 16 || off + 8 + body_len > got) break;
-    const uint8_t* body = data.data() + off + 8;
-    if (crc32_update(0, body, body_len) != crc) break;
-    uint64_t region, seq;
-    std::memcpy(&region, body, 8);
-    std::memcpy(&seq, body + 8, 8);
-    out.append(py::make_tuple(region, seq,
-        py::bytes(reinterpret_cast<const char*>(body + 16), body_len - 16)));
-    off += 8 + body_len;
-  }
+  for (const auto& f : frames)
+    out.append(py::make_tuple(
+        f.region, f.seq,
+        py::bytes(reinterpret_cast<const char*>(f.payload), f.plen)));
   return out;
+}
+
+// zlib-compatible CRC-32 of a bytes-like object. impl: "auto" (what the WAL
+// uses), "table" (slice-by-8) or "clmul" (raises on a CPU without it).
+static uint32_t py_crc32(py::object data, uint32_t init, const std::string& impl) {
+  PayloadView v;
+  v.acquire(data.ptr());
+  if (impl == "auto") return gdb_wal::crc32_update(init, v.p, v.n);
+  if (impl == "table") return gdb_wal::crc32_table(init, v.p, v.n);
+  if (impl == "clmul") return gdb_wal::crc32_clmul(init, v.p, v.n);
+  throw std::invalid_argument("crc32: impl must be auto, table or clmul");
 }
 
 // ---------------------------------------------------------------- snappy
@@ -1419,13 +1395,34 @@ PYBIND11_MODULE(_native, m) {
       .def("field_names", &LineParser::field_names)
       .def("register_tagset", &LineParser::register_tagset)
       .def("register_field", &LineParser::register_field);
-  py::class_<WalWriter>(m, "WalWriter")
+  py::class_<gdb_wal::WalWriter>(m, "WalWriter")
       .def(py::init<>())
-      .def("open_segment", &WalWriter::open_segment)
-      .def("close_segment", &WalWriter::close_segment)
-      .def("append", &WalWriter::append)
-      .def("commit", &WalWriter::commit, py::arg("sync") = true)
-      .def("segment_bytes", &WalWriter::segment_bytes);
+      .def("open_segment", &gdb_wal::WalWriter::open_segment,
+           py::call_guard<py::gil_scoped_release>())
+      .def("close_segment", &gdb_wal::WalWriter::close_segment,
+           py::arg("sync") = false, py::call_guard<py::gil_scoped_release>())
+      .def("rotate", &gdb_wal::WalWriter::rotate, py::arg("path"),
+           py::arg("sync") = false, py::call_guard<py::gil_scoped_release>())
+      .def("append", &wal_writer_append)
+      .def("commit", &gdb_wal::WalWriter::commit, py::arg("sync") = true,
+           py::call_guard<py::gil_scoped_release>())
+      // the accessors take the writer's mutex, which a write or sync in
+      // another thread may hold for a while: wait for it without the GIL
+      .def("segment_bytes", &gdb_wal::WalWriter::segment_bytes,
+           py::call_guard<py::gil_scoped_release>())
+      .def("unsynced_bytes", &gdb_wal::WalWriter::unsynced_bytes,
+           py::call_guard<py::gil_scoped_release>())
+      .def("sync_count", &gdb_wal::WalWriter::sync_count,
+           py::call_guard<py::gil_scoped_release>());
+  m.def("wal_append_commit", &wal_append_commit, py::arg("writers"),
+        py::arg("region_ids"), py::arg("seqs"), py::arg("payloads"),
+        py::arg("sync") = false);
+  m.def("crc32", &py_crc32, py::arg("data"), py::arg("init") = 0,
+        py::arg("impl") = "auto");
+  m.def("crc32_have_clmul", &gdb_wal::crc32_have_clmul);
+  m.def("crc32_force_table", [](bool on) {
+    gdb_wal::crc32_force_table_flag().store(on);
+  }, "measurement switch: make the \"auto\" CRC path use the table");
   m.def("wal_read_segment", &wal_read_segment);
   m.def("snappy_uncompress", &py_snappy_uncompress);
   m.def("pack_str_col", &pack_str_col);

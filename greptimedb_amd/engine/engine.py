@@ -51,6 +51,9 @@ class TableState:
     regions: list = field(default_factory=list)
     append_mode: bool = False
     rule: object = None   # cached PartitionRule (parallel/partition.py)
+    # (copy of `regions`, the same in lock order, their ids): what the
+    # fused write path needs per batch, rebuilt when `regions` changes
+    fused_order: tuple = field(default=None, repr=False, compare=False)
 
 
 class MitoEngine:
@@ -406,12 +409,18 @@ class MitoEngine:
 
     def write_regions_fused(self, table: TableState, slot, n: int, nf: int,
                             counts, mins, maxs, payloads: list,
-                            durable: bool = True) -> None:
+                            durable: bool = True,
+                            wal_batch: bool = False) -> None:
         """K16 fast path fed by LineParser.ingest_batch: the routed batch
         sits in one packed block (`slot.host`, layout of
         ops.cpu_ref.packed_segments) next to ready WAL payloads and
         per-region counts/min/max. Python appends the WAL entries, reserves
         rows under the region locks and makes ONE device call.
+
+        wal_batch: the entries are appended AND committed here by
+        Wal.append_commit_many (one GIL-free native call; the caller does
+        not call commit_wal for this batch). Off: one Wal.append per region,
+        and the caller commits.
 
         slot.dev set: ops.scatter_append_packed — one non-blocking copy of
         the pinned block plus one kernel on the current stream (on a CPU
@@ -426,13 +435,33 @@ class MitoEngine:
         from greptimedb_amd.ops import kernels as ops
 
         regions: list[Region] = table.regions
-        counts = [int(c) for c in counts]
+        cached = table.fused_order
+        # Region has no __eq__, so the list comparison is one identity test
+        # per element in C; it also sees a region replaced in place
+        # (migration), which the identity of the list would not
+        if cached is None or cached[0] != regions:
+            cached = table.fused_order = (
+                list(regions),
+                tuple(sorted(regions, key=lambda r: r.region_id)),
+                tuple(r.region_id for r in regions))
+        ordered = cached[1]
+        counts, mins, maxs = (
+            a.tolist() if hasattr(a, "tolist") else [int(v) for v in a]
+            for a in (counts, mins, maxs))
         seqs = [0] * len(regions)
-        if durable:
+        if durable and wal_batch:
+            # the whole batch's frames in one native call: written (and
+            # synced with wal_sync) before the rows are reserved below
+            live = [k for k, p in enumerate(payloads) if p is not None]
+            rids = cached[2]
+            got = self.wal.append_commit_many(
+                [rids[k] for k in live], [payloads[k] for k in live])
+            for k, seq in zip(live, got):
+                seqs[k] = seq
+        elif durable:
             for k, p in enumerate(payloads):
                 if p is not None:
                     seqs[k] = self.wal.append(regions[k].region_id, p)
-        ordered = sorted(regions, key=lambda r: r.region_id)
         for r in ordered:
             r.lock.acquire()
         try:
@@ -467,7 +496,7 @@ class MitoEngine:
                     continue
                 mem = region.memtable
                 mem.len = bases[k] + m
-                mn, mx = int(mins[k]), int(maxs[k])
+                mn, mx = mins[k], maxs[k]
                 mem.min_ts = mn if mem.min_ts is None else min(mem.min_ts, mn)
                 mem.max_ts = mx if mem.max_ts is None else max(mem.max_ts, mx)
                 region.last_seq = max(region.last_seq, seqs[k])

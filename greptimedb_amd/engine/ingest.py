@@ -11,19 +11,21 @@ Steady state (bulk path, every row of a known series of one table) is ONE
 native call, LineParser.ingest_batch (csrc/ingest_core.h), with the GIL
 released: parse straight into a packed staging block, route each row through
 the per-table sid LUTs (region, local code, destination offset, ts → ms),
-and build the per-region WAL payloads. Python then only appends the WAL
-entries, reserves memtable rows under the region locks and makes one device
-call (engine.write_regions_fused → ops.scatter_append_packed: one
-non-blocking copy of the pinned block + one kernel), commits the WAL and
-checks flush thresholds. The staging blocks form a ring of STAGE_RING
-pinned/device pairs per Ingestor; an event recorded behind each launch is
-waited on before its block is refilled, so the host never overwrites a
-block its DMA has not read. Anything the native call cannot route — a new
+and build the per-region WAL payloads. Python then only writes the batch's
+WAL frames through (Wal.append_commit_many: one more GIL-free native call
+that checksums and writes them straight from the payload buffers), reserves
+memtable rows under the region locks, makes one device call
+(engine.write_regions_fused → ops.scatter_append_packed: one non-blocking
+copy of the pinned block + one kernel) and checks flush thresholds. The
+staging blocks form a ring of STAGE_RING pinned/device pairs per Ingestor;
+an event recorded behind each launch is waited on before its block is
+refilled, so the host never overwrites a block its DMA has not read. Anything the native call cannot route — a new
 series or field, another table's rows, remote-owned series, more than 16
 regions, text columns — comes back as the ordinary parse() result and takes
 the general path below without being parsed twice. `Ingestor._fused = False`
 switches the whole fast path off; `_packed = False` keeps the fused pass but
-uploads the block's segments through scatter_append.
+uploads the block's segments through scatter_append; `_wal_batch = False`
+goes back to one Wal.append per region plus commit_wal.
 
 Partitioning: hash(encoded pk) % n_regions (the default when no PARTITION ON
 clause — reference uses MultiDimPartitionRule; explicit partition rules live
@@ -112,6 +114,10 @@ class Ingestor:
         # Off on GPU = the stage is plain host memory and its segments go
         # through scatter_append (CPU engines always read the block in place)
         self._packed = True
+        # durable fused batches append and commit their WAL frames in one
+        # native call (Wal.append_commit_many); off = one Wal.append per
+        # region plus commit_wal
+        self._wal_batch = True
         self._ring: list[_StageSlot] = []   # staging ring, STAGE_RING slots
         self._ring_pos = 0
         self._fused_st = None    # table the fused LUTs describe
@@ -356,11 +362,13 @@ class Ingestor:
         if n == 0:
             return 0
         engine = self.engine
+        wal_batch = self._wal_batch
         engine.write_regions_fused(st0, slot, n, nf, counts, mins, maxs,
-                                   payloads, durable=self.durable)
+                                   payloads, durable=self.durable,
+                                   wal_batch=wal_batch)
         slot.busy = slot.event is not None
         self._ring_pos = (self._ring_pos + 1) % len(self._ring)
-        if self.durable:
+        if self.durable and not wal_batch:
             engine.commit_wal()
         engine.maybe_flush()
         self.rows_ingested += n
