@@ -49,6 +49,14 @@ void launch_rle_expand_indices(const int64_t*, int64_t, const uint8_t*, int,
                                int32_t*, int64_t, hipStream_t);
 void launch_gorilla_decode(const uint8_t*, const int64_t*, const int64_t*,
                            int64_t, int64_t*, double*, int64_t, hipStream_t);
+int gorilla_encode_max_block();
+void launch_gorilla_scale(const double*, int64_t, unsigned*, hipStream_t);
+void launch_gorilla_widths(const int64_t*, const double*, int64_t, int, int,
+                           const unsigned*, uint8_t*, int64_t*, int64_t,
+                           hipStream_t);
+void launch_gorilla_write(const int64_t*, const double*, int64_t, int,
+                          const unsigned*, const uint8_t*, const int64_t*,
+                          uint8_t*, int64_t, hipStream_t);
 void launch_bucket_cells(
     const int64_t*, const int32_t*, const int32_t*, int, int64_t, int64_t,
     int64_t, int64_t, int, int64_t, int32_t*, hipStream_t);
@@ -373,6 +381,58 @@ std::vector<torch::Tensor> gorilla_decode(torch::Tensor blob,
   return {ts, vals};
 }
 
+// K20: Gorilla/delta block encode on device → (blob u8, block_off i64[B],
+// out_off i64[B]), byte for byte what engine/gorilla.py pack() returns.
+// `vals` None packs like a column of zeros (the ts-only pack). One
+// device-to-host read (the total size) sizes the blob.
+std::vector<torch::Tensor> gorilla_encode(torch::Tensor ts,
+                                          c10::optional<torch::Tensor> vals,
+                                          int64_t block, bool pack_ts) {
+  CHECK_GPU(ts); CHECK_CONTIG(ts);
+  TORCH_CHECK(ts.scalar_type() == torch::kInt64, "ts must be int64");
+  TORCH_CHECK(ts.dim() == 1, "ts must be one-dimensional");
+  TORCH_CHECK(block >= 1 && block <= gdb_hip::gorilla_encode_max_block(),
+              "gorilla_encode: block must be in [1, ",
+              gdb_hip::gorilla_encode_max_block(), "], got ", block);
+  const int64_t n = ts.numel();
+  const double* vals_p = nullptr;
+  if (vals.has_value()) {
+    const torch::Tensor& v = *vals;
+    CHECK_GPU(v); CHECK_CONTIG(v);
+    TORCH_CHECK(v.scalar_type() == torch::kFloat64, "vals must be float64");
+    TORCH_CHECK(v.dim() == 1 && v.numel() == n, "vals must match ts in length");
+    TORCH_CHECK(v.device() == ts.device(), "ts and vals on different devices");
+    vals_p = v.data_ptr<double>();
+  }
+  auto opts_u8 = ts.options().dtype(torch::kUInt8);
+  auto opts_i64 = ts.options().dtype(torch::kInt64);
+  const int64_t B = (n + block - 1) / block;
+  TORCH_CHECK(B <= INT32_MAX, "gorilla_encode: too many blocks");
+  if (B == 0)
+    return {torch::zeros({16}, opts_u8), torch::empty({0}, opts_i64),
+            torch::empty({0}, opts_i64)};
+  auto stream = at::cuda::getCurrentHIPStream().stream();
+  auto fail = torch::zeros({1}, ts.options().dtype(torch::kInt32));
+  auto* fail_p = reinterpret_cast<unsigned*>(fail.data_ptr<int32_t>());
+  if (vals_p != nullptr)
+    gdb_hip::launch_gorilla_scale(vals_p, n, fail_p, stream);
+  auto bits = torch::empty({B, 2}, opts_u8);
+  auto sizes = torch::empty({B}, opts_i64);
+  gdb_hip::launch_gorilla_widths(
+      ts.data_ptr<int64_t>(), vals_p, n, (int)block, pack_ts ? 1 : 0, fail_p,
+      bits.data_ptr<uint8_t>(), sizes.data_ptr<int64_t>(), B, stream);
+  auto ends = torch::cumsum(sizes, 0);
+  auto block_off = ends - sizes;
+  const int64_t total = ends[B - 1].item<int64_t>() + 16;
+  auto blob = torch::zeros({total}, opts_u8);
+  gdb_hip::launch_gorilla_write(
+      ts.data_ptr<int64_t>(), vals_p, n, (int)block, fail_p,
+      bits.data_ptr<uint8_t>(), block_off.data_ptr<int64_t>(),
+      blob.data_ptr<uint8_t>(), B, stream);
+  auto out_off = torch::arange(B, opts_i64) * block;
+  return {blob, block_off, out_off};
+}
+
 // Phase A of the bucket aggregate on its own: the (slot, bucket) cell id of
 // every row, slot * n_buckets + bucket, or -1 where the row is filtered out.
 torch::Tensor bucket_cells(
@@ -543,6 +603,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ts_bucket_agg_finish", &ts_bucket_agg_finish, "decode raw accumulators");
   m.def("rle_expand_indices", &rle_expand_indices, "K11 hybrid RLE expand");
   m.def("gorilla_decode", &gorilla_decode, "K20 gorilla block decode");
+  m.def("gorilla_encode", &gorilla_encode, "K20 gorilla block encode",
+        py::arg("ts"), py::arg("vals"), py::arg("block"), py::arg("pack_ts"));
   m.def("filter_series_time", &filter_series_time, "series/time filter mask");
   m.def("dedup_mark_last", &dedup_mark_last, "last-row dedup marker");
   m.def("series_last_ts", &series_last_ts, "per-slot max-ts accumulate (lastpoint)");

@@ -11,6 +11,8 @@
 //  - dedup_mark_last_kernel : K4 last_row marker on (series, ts)-sorted data.
 //  - quantile_{hist,pick,next,finish}_kernel : K21 exact grouped order
 //    statistics by radix-histogram selection over bucket cells.
+//  - gorilla_decode_kernel / gorilla_{scale,widths,write}_kernel : K20 cold
+//    tier, fixed-width-per-block delta codec, decoded and encoded in HBM.
 //
 // Design notes (cdna_hip_programming.md):
 //  * 256-thread blocks (4 waves of 64), grid-stride, grid capped at
@@ -1228,21 +1230,22 @@ __global__ void rle_expand_indices_kernel(
   }
 }
 
-// ------------------------------------------------- K20 Gorilla / delta-delta
-// Block format (engine/gorilla.py packs on host at spill time):
-//   per block of BLK values: header {int64 first_ts, int64 first_delta,
-//   u64 first_val_bits, int32 nbits_ts, int32 nbits_val...} — here the
-//   simple fixed-width variant: delta-of-delta stored with per-block bit
-//   width, XOR'd value bits with per-block width (CDNA4-friendly: fixed
-//   widths per block → branchless bit extraction, one thread per value
-//   with a per-block prefix scan done at pack time so decode is O(1)).
-// Layout per block in `blob`:
-//   [i64 base_ts][i64 base_dod_acc? not needed][u64 base_val]
-//   [u8 ts_bits][u8 val_bits][u16 count][pad to 8B]
-//   [packed ts dods (zigzag, ts_bits each)][packed val xors (val_bits each)]
-// ts[i] = base_ts + prefix_sum(deltas); to keep decode parallel the packer
-// stores ABSOLUTE deltas from base (ts[i] - base_ts) instead of
-// delta-of-delta when that fits the same width; flag in high bit of ts_bits.
+// ------------------------------------------------------ K20 Gorilla / delta
+// Block format (engine/gorilla.py is the specification; its pack() is the
+// host packer and the encoder kernels below write the same bytes). Widths
+// are fixed per block, so every value's bit position is O(1) and both
+// directions run one thread per value / per output word.
+// Layout per block of `count` values in `blob` (blocks start 8B-aligned):
+//   [i64 base_ts][u64 base_val][u8 ts_bits][u8 val_bits][u16 count]
+//   [u8 val_mode][u8 scale_k][2B pad]                          (24 bytes)
+//   [count-1 × zigzag(ts[i] - base_ts), ts_bits each, LSB first, pad to 8B]
+//   [count-1 × value payload, val_bits each, LSB first, pad to 8B]
+// val_mode 0: base_val = bits(val[0]), payload = bits(val[i]) ^ base_val.
+// val_mode 1: base_val = (i64)rint(val[0]·10^scale_k), payload =
+//   zigzag(rint(val[i]·10^scale_k) - base_val); decodes as int / 10^scale_k.
+// Deltas are ABSOLUTE from the block base (not delta-of-delta), so no
+// prefix sum is needed. The blob ends in 16 zero bytes: the decoder reads
+// up to 9 bytes past the last packed bit.
 __global__ void gorilla_decode_kernel(
     const uint8_t* __restrict__ blob,
     const int64_t* __restrict__ block_off,   // [B] byte offset of each block
@@ -1323,6 +1326,206 @@ __global__ void gorilla_decode_kernel(
   }
 }
 
+// ------------------------------------------------------------ K20 encoder
+// Three launches write what gorilla.pack() writes, byte for byte:
+//   gorilla_scale_kernel  : one reduction over the column → which 10^k
+//                           scales (k = 0..4) reproduce every value;
+//   gorilla_widths_kernel : one workgroup per codec block → ts_bits,
+//                           val_bits and the block's byte size;
+//   gorilla_write_kernel  : one workgroup per codec block → header, then
+//                           each thread gathers the values overlapping its
+//                           64-bit output word from LDS and stores it whole.
+// The exclusive scan of the sizes between the last two runs in the binding.
+constexpr int GENC_THREADS = 256;
+constexpr int GENC_MAX_BLOCK = 4096;        // values per codec block (LDS stage)
+constexpr unsigned GENC_NONFINITE = 1u << 5;
+constexpr unsigned GENC_ALL_SCALES = 0x1Fu;
+
+DEV_INLINE uint64_t zigzag64(int64_t d) {
+  return ((uint64_t)d << 1) ^ (uint64_t)(d >> 63);
+}
+
+DEV_INLINE double gorilla_pow10(int k) {   // exact in f64 for k <= 4
+  double s = 1.0;
+  for (int q = 0; q < k; q++) s *= 10.0;
+  return s;
+}
+
+// fail word → (val_mode, scale_k). No value column packs like a column of
+// zeros: scaled mode at k = 0.
+DEV_INLINE void gorilla_mode(const double* vals, const unsigned* fail,
+                             int& val_mode, int& scale_k) {
+  val_mode = 1;
+  scale_k = 0;
+  if (vals == nullptr) return;
+  const unsigned f = *fail;
+  if (!(f & GENC_NONFINITE)) {
+    for (int k = 0; k < 5; k++) {
+      if (!((f >> k) & 1u)) { scale_k = k; return; }
+    }
+  }
+  val_mode = 0;
+}
+
+// gorilla._detect_scale: bit k of *fail is set when some value does not
+// survive (double)(int64)rint(v·10^k) / 10^k bit for bit, or |v·10^k| is
+// not below 2^47; GENC_NONFINITE when some value is NaN or ±inf. The
+// multiply, rint and divide are separately rounded IEEE operations.
+__global__ void __launch_bounds__(GENC_THREADS) gorilla_scale_kernel(
+    const double* __restrict__ vals, int64_t n, unsigned* __restrict__ fail) {
+#pragma clang fp contract(off)
+  unsigned f = 0;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += stride) {
+    const double v = vals[i];
+    const uint64_t bits = (uint64_t)__double_as_longlong(v);
+    if ((bits & 0x7FF0000000000000ULL) == 0x7FF0000000000000ULL) {
+      f |= GENC_NONFINITE | GENC_ALL_SCALES;
+      continue;
+    }
+    double scale = 1.0;
+    for (int k = 0; k < 5; k++) {
+      const double sv = v * scale;
+      // an out-of-range (or overflowed) product is never converted
+      if (!(fabs(sv) < 140737488355328.0)) {          // 2^47
+        f |= 1u << k;
+      } else {
+        const double back = (double)(int64_t)rint(sv) / scale;
+        if ((uint64_t)__double_as_longlong(back) != bits) f |= 1u << k;
+      }
+      scale *= 10.0;
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) f |= __shfl_xor(f, off, 64);
+  if ((threadIdx.x & 63) == 0 && f) atomicOr(fail, f);
+}
+
+// payload of value i of the codec block starting at row s
+DEV_INLINE uint64_t gorilla_val_payload(const double* __restrict__ vals,
+                                        int64_t s, int64_t i, int val_mode,
+                                        double scale) {
+#pragma clang fp contract(off)
+  if (vals == nullptr) return 0;
+  if (val_mode == 1) {
+    // scaled mode was chosen, so every product is finite and below 2^47
+    const int64_t base = (int64_t)rint(vals[s] * scale);
+    return zigzag64((int64_t)rint(vals[i] * scale) - base);
+  }
+  return (uint64_t)__double_as_longlong(vals[i]) ^
+         (uint64_t)__double_as_longlong(vals[s]);
+}
+
+DEV_INLINE uint64_t gorilla_ts_payload(const int64_t* __restrict__ ts,
+                                       int64_t s, int64_t i) {
+  // wrap-around difference, like numpy's int64
+  return zigzag64((int64_t)((uint64_t)ts[i] - (uint64_t)ts[s]));
+}
+
+DEV_INLINE int bit_length64(uint64_t x) { return x ? 64 - __clzll(x) : 0; }
+
+// bits[2b] = ts_bits, bits[2b+1] = val_bits, sizes[b] = bytes of block b.
+// bit_length(max) == bit_length(OR), so the widths are an OR reduction.
+__global__ void __launch_bounds__(GENC_THREADS) gorilla_widths_kernel(
+    const int64_t* __restrict__ ts, const double* __restrict__ vals,
+    int64_t n, int block, int pack_ts, const unsigned* __restrict__ fail,
+    uint8_t* __restrict__ bits, int64_t* __restrict__ sizes) {
+  __shared__ uint64_t red[2][GENC_THREADS / 64];
+  const int64_t s = (int64_t)blockIdx.x * block;
+  const int count = (int)((n - s < block) ? (n - s) : block);
+  int val_mode, scale_k;
+  gorilla_mode(vals, fail, val_mode, scale_k);
+  const double scale = gorilla_pow10(scale_k);
+  uint64_t or_ts = 0, or_val = 0;
+  for (int r = 1 + (int)threadIdx.x; r < count; r += GENC_THREADS) {
+    if (pack_ts) or_ts |= gorilla_ts_payload(ts, s, s + r);
+    or_val |= gorilla_val_payload(vals, s, s + r, val_mode, scale);
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    or_ts |= __shfl_xor(or_ts, off, 64);
+    or_val |= __shfl_xor(or_val, off, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    red[0][threadIdx.x >> 6] = or_ts;
+    red[1][threadIdx.x >> 6] = or_val;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < GENC_THREADS / 64; w++) {
+      or_ts |= red[0][w];
+      or_val |= red[1][w];
+    }
+    const int tb = bit_length64(or_ts), vb = bit_length64(or_val);
+    const int64_t k = count - 1;
+    bits[2 * (int64_t)blockIdx.x] = (uint8_t)tb;
+    bits[2 * (int64_t)blockIdx.x + 1] = (uint8_t)vb;
+    sizes[blockIdx.x] = 24 + 8 * ((k * tb + 63) / 64) + 8 * ((k * vb + 63) / 64);
+  }
+}
+
+// k values of w bits each (staged in LDS, no bits above w) → ceil(k·w/64)
+// whole little-endian words; bits past the last value are zero.
+DEV_INLINE void gorilla_pack_section(const uint64_t* stage, int k, int w,
+                                     uint64_t* __restrict__ out) {
+  const int words = (k * w + 63) >> 6;
+  for (int j = (int)threadIdx.x; j < words; j += GENC_THREADS) {
+    const int lo = j << 6;
+    uint64_t acc = 0;
+    for (int i = lo / w; i < k && i * w < lo + 64; i++) {
+      const int sh = i * w - lo;             // -63 .. 63
+      const uint64_t v = stage[i];
+      acc |= (sh >= 0) ? (v << sh) : (v >> -sh);
+    }
+    out[j] = acc;
+  }
+}
+
+__global__ void __launch_bounds__(GENC_THREADS) gorilla_write_kernel(
+    const int64_t* __restrict__ ts, const double* __restrict__ vals,
+    int64_t n, int block, const unsigned* __restrict__ fail,
+    const uint8_t* __restrict__ bits, const int64_t* __restrict__ block_off,
+    uint8_t* __restrict__ blob) {
+  __shared__ uint64_t stage[GENC_MAX_BLOCK];
+  const int64_t s = (int64_t)blockIdx.x * block;
+  const int count = (int)((n - s < block) ? (n - s) : block);
+  const int k = count - 1;
+  int val_mode, scale_k;
+  gorilla_mode(vals, fail, val_mode, scale_k);
+  const double scale = gorilla_pow10(scale_k);
+  const int tb = bits[2 * (int64_t)blockIdx.x];
+  const int vb = bits[2 * (int64_t)blockIdx.x + 1];
+  // block offsets are sums of multiples of 8, so every store is aligned
+  uint64_t* out = reinterpret_cast<uint64_t*>(blob + block_off[blockIdx.x]);
+  if (threadIdx.x == 0) {
+    uint64_t base_val = 0;
+    if (vals != nullptr) {
+#pragma clang fp contract(off)
+      base_val = (val_mode == 1)
+          ? (uint64_t)(int64_t)rint(vals[s] * scale)
+          : (uint64_t)__double_as_longlong(vals[s]);
+    }
+    out[0] = (uint64_t)ts[s];
+    out[1] = base_val;
+    out[2] = (uint64_t)tb | ((uint64_t)vb << 8) | ((uint64_t)count << 16) |
+             ((uint64_t)val_mode << 32) | ((uint64_t)scale_k << 40);
+  }
+  out += 3;
+  if (tb) {                                   // uniform across the workgroup
+    for (int r = (int)threadIdx.x; r < k; r += GENC_THREADS)
+      stage[r] = gorilla_ts_payload(ts, s, s + 1 + r);
+    __syncthreads();
+    gorilla_pack_section(stage, k, tb, out);
+    __syncthreads();
+    out += (k * tb + 63) >> 6;
+  }
+  if (vb) {
+    for (int r = (int)threadIdx.x; r < k; r += GENC_THREADS)
+      stage[r] = gorilla_val_payload(vals, s, s + 1 + r, val_mode, scale);
+    __syncthreads();
+    gorilla_pack_section(stage, k, vb, out);
+  }
+}
+
 void launch_rle_expand_indices(
     const int64_t* runs, int64_t R, const uint8_t* blob, int bw,
     int32_t* out, int64_t n, hipStream_t stream) {
@@ -1337,6 +1540,33 @@ void launch_gorilla_decode(
   hipLaunchKernelGGL(gorilla_decode_kernel, dim3(grid_for(n, 256)),
                      dim3(256), 0, stream, blob, block_off, out_off, B,
                      out_ts, out_val, n);
+}
+
+int gorilla_encode_max_block() { return GENC_MAX_BLOCK; }
+
+// `fail` must be zeroed by the caller; `vals` may be null (no value column).
+void launch_gorilla_scale(const double* vals, int64_t n, unsigned* fail,
+                          hipStream_t stream) {
+  hipLaunchKernelGGL(gorilla_scale_kernel, dim3(grid_for(n, GENC_THREADS)),
+                     dim3(GENC_THREADS), 0, stream, vals, n, fail);
+}
+
+void launch_gorilla_widths(
+    const int64_t* ts, const double* vals, int64_t n, int block, int pack_ts,
+    const unsigned* fail, uint8_t* bits, int64_t* sizes, int64_t B,
+    hipStream_t stream) {
+  hipLaunchKernelGGL(gorilla_widths_kernel, dim3((unsigned)B),
+                     dim3(GENC_THREADS), 0, stream, ts, vals, n, block,
+                     pack_ts, fail, bits, sizes);
+}
+
+void launch_gorilla_write(
+    const int64_t* ts, const double* vals, int64_t n, int block,
+    const unsigned* fail, const uint8_t* bits, const int64_t* block_off,
+    uint8_t* blob, int64_t B, hipStream_t stream) {
+  hipLaunchKernelGGL(gorilla_write_kernel, dim3((unsigned)B),
+                     dim3(GENC_THREADS), 0, stream, ts, vals, n, block, fail,
+                     bits, block_off, blob);
 }
 
 }  // namespace gdb_hip

@@ -198,9 +198,33 @@ class GorillaBatch:
         self.blob, self.block_off, self.out_off, self.n = \
             pack(ts, vals, block, pack_ts=pack_ts)
 
+    @classmethod
+    def from_device(cls, ts_t: torch.Tensor, vals_t: torch.Tensor | None,
+                    block: int = BLOCK, pack_ts: bool = True):
+        """Pack tensors where they live (ops.gorilla_encode: the HIP encoder
+        for CUDA tensors). blob/block_off/out_off are then tensors on that
+        device, with pack()'s exact bytes, and a CUDA batch decodes without
+        an upload. `vals_t` None packs like a column of zeros."""
+        from greptimedb_amd import ops
+        self = cls.__new__(cls)
+        self.blob, self.block_off, self.out_off, self.n = \
+            ops.gorilla_encode(ts_t, vals_t, block, pack_ts)
+        return self
+
     @property
     def nbytes(self) -> int:
+        if torch.is_tensor(self.blob):
+            return int(self.blob.numel())
         return len(self.blob)
 
     def decode(self, device: str = "cpu"):
-        return decode(self.blob, self.block_off, self.out_off, self.n, device)
+        if not torch.is_tensor(self.blob):
+            return decode(self.blob, self.block_off, self.out_off, self.n,
+                          device)
+        if self.blob.is_cuda:
+            from greptimedb_amd import _hip_ops
+            ts, vals = _hip_ops.gorilla_decode(self.blob, self.block_off,
+                                               self.out_off, self.n)
+            return ts, vals
+        return decode(self.blob.numpy().tobytes(), self.block_off.numpy(),
+                      self.out_off.numpy(), self.n, device)

@@ -165,6 +165,9 @@ class SstBatch:
             return sum(g.nbytes for k, g in self._gorilla.items()
                        if k != "__n")
         from greptimedb_amd.engine import gorilla
+        from greptimedb_amd.ops import hip_ops_available
+        if self.ts.is_cuda and self._device_encode and hip_ops_available():
+            return self._compress_device(gorilla)
         ts_h = self.ts.cpu().numpy()
         packs = {"__n": int(self.ts.numel())}
         # ts packed ONCE; field blocks skip the ts section (ts_bits=0)
@@ -177,6 +180,31 @@ class SstBatch:
         self._seq_h = self.seq.cpu().numpy() if self.seq is not None else None
         self.ts = None
         self.series = None
+        self.fields = None
+        self.seq = None
+        return sum(g.nbytes for k, g in packs.items() if k != "__n")
+
+    # False restores the host packer for CUDA batches (A/B switch, in the
+    # style of Executor._device_quantile); CPU batches always pack on host.
+    _device_encode = True
+
+    def _compress_device(self, gorilla) -> int:
+        """Cold tier without leaving HBM: the HIP encoder packs ts, every
+        field and seq where they live; `series` (i32, counted by the caller)
+        stays as it is. Nothing is copied to the host."""
+        packs = {"__n": int(self.ts.numel())}
+        from_dev = gorilla.GorillaBatch.from_device
+        packs["__ts"] = from_dev(self.ts, None)
+        for i in range(self.fields.shape[0]):
+            packs[f"f{i}"] = from_dev(self.ts, self.fields[i], pack_ts=False)
+        if self.seq is not None:
+            # any int64 survives the integer (ts) path bit for bit
+            self._seq_dtype = self.seq.dtype
+            packs["__seq"] = from_dev(self.seq.to(torch.int64), None)
+        self._gorilla = packs
+        self._series_h = None
+        self._seq_h = None
+        self.ts = None
         self.fields = None
         self.seq = None
         return sum(g.nbytes for k, g in packs.items() if k != "__n")
@@ -194,7 +222,7 @@ class SstBatch:
             return self
         import torch as _torch
         packs = self._gorilla
-        nf = len([k for k in packs if k not in ("__n", "__ts")])
+        nf = len([k for k in packs if not k.startswith("__")])
         n = packs["__n"]
         fields = _torch.empty((nf, n), dtype=_torch.float64, device=device)
         ts, _zero = packs["__ts"].decode(device)
@@ -203,8 +231,14 @@ class SstBatch:
             fields[i] = v
         self.ts = ts.to(device)
         self.fields = fields
-        self.series = _torch.as_tensor(self._series_h).to(device)
-        if self._seq_h is not None:
+        if self.series is None:        # host pack; a device pack kept it
+            self.series = _torch.as_tensor(self._series_h).to(device)
+        else:
+            self.series = self.series.to(device)
+        if "__seq" in packs:
+            seq, _zero = packs["__seq"].decode(device)
+            self.seq = seq.to(device=device, dtype=self._seq_dtype)
+        elif self._seq_h is not None:
             self.seq = _torch.as_tensor(self._seq_h).to(device)
         self._gorilla = None
         return self

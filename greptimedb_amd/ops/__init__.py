@@ -11,6 +11,7 @@ from greptimedb_amd.ops.kernels import (  # noqa: F401
     bucket_cells,
     dedup_mark_last,
     filter_series_time,
+    gorilla_encode,
     grouped_quantile,
     hip_ops_available,
     prom_range_eval,

@@ -332,6 +332,20 @@ def dedup_mark_last(series, ts):
     return keep
 
 
+def gorilla_encode(ts, vals, block, pack_ts=True):
+    """Oracle for kernels.gorilla_encode (K20): gorilla.pack is the
+    specification. → (blob u8, block_off i64[B], out_off i64[B], n);
+    `vals` None packs like a column of zeros."""
+    import numpy as np
+    from greptimedb_amd.engine import gorilla
+    ts_h = ts.numpy()
+    v_h = np.zeros(len(ts_h)) if vals is None else vals.numpy()
+    blob, block_off, out_off, n = gorilla.pack(ts_h, v_h, block,
+                                               pack_ts=pack_ts)
+    return (torch.as_tensor(np.frombuffer(blob, dtype=np.uint8).copy()),
+            torch.as_tensor(block_off), torch.as_tensor(out_off), n)
+
+
 def scatter_append(ts, series, fields, region_of, dst_off,
                    dst_ts, dst_se, dst_fields):
     """Oracle for kernels.scatter_append (K16): routed bulk memtable write."""

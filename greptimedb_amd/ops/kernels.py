@@ -4,6 +4,7 @@ from __future__ import annotations
 
 import torch
 
+from greptimedb_amd.engine import gorilla
 from greptimedb_amd.ops import cpu_ref
 from greptimedb_amd.utils.errors import NativeExtensionMissing
 
@@ -215,6 +216,20 @@ def series_last(sources, slot_lut, ts_lo, ts_hi, n_slots):
     none = best_src < 0
     best_ts = torch.where(none, torch.full_like(best_ts, -(1 << 63) + 1), best_ts)
     return best_ts.cpu(), best_src.cpu(), best_row.cpu()
+
+
+def gorilla_encode(ts, vals, block=gorilla.BLOCK, pack_ts=True):
+    """K20 cold-tier encode: (ts i64[n], vals f64[n] or None) →
+    (blob u8, block_off i64[B], out_off i64[B], n), byte for byte what
+    gorilla.pack returns; `vals` None packs like a column of zeros without
+    allocating one. On GPU the outputs stay on the device (1 ≤ block ≤ 4096);
+    the only host read is the blob's total size."""
+    if ts.is_cuda:
+        blob, block_off, out_off = _require_hip().gorilla_encode(
+            ts.contiguous(), None if vals is None else vals.contiguous(),
+            int(block), bool(pack_ts))
+        return blob, block_off, out_off, int(ts.numel())
+    return cpu_ref.gorilla_encode(ts, vals, int(block), bool(pack_ts))
 
 
 def scatter_append(ts, series, fields, region_of, dst_off,
