@@ -24,6 +24,8 @@ void launch_filter_series_time(
     const int64_t*, const int32_t*, const int32_t*, int, int64_t, int64_t,
     int64_t, bool*, hipStream_t);
 void launch_dedup_mark_last(const int32_t*, const int64_t*, int64_t, bool*, hipStream_t);
+void launch_merge_last_non_null(const int64_t*, int64_t, const double*, int64_t,
+                                int, double*, hipStream_t);
 void launch_bucket_agg2(
     const int64_t*, const int32_t*, const double*, int64_t, const int32_t*, int,
     const int32_t*, int, int64_t, int64_t, int64_t, int64_t, int, int, int64_t,
@@ -189,6 +191,38 @@ torch::Tensor dedup_mark_last(torch::Tensor series, torch::Tensor ts) {
       series.data_ptr<int32_t>(), ts.data_ptr<int64_t>(), n,
       keep.data_ptr<bool>(), stream);
   return keep;
+}
+
+// last_non_null merge over (series, ts, seq)-sorted rows: kidx i64[g] = the
+// last row of every (series, ts) group, merged f64[nf, g] = per field the
+// newest non-NaN value of the group (the last row's bits if there is none).
+// The group count is data dependent, so nonzero() reads it back, as the
+// LastRow path's own nonzero does.
+std::tuple<torch::Tensor, torch::Tensor> merge_last_non_null(
+    torch::Tensor series, torch::Tensor ts, torch::Tensor fields) {
+  CHECK_GPU(series); CHECK_GPU(ts); CHECK_GPU(fields);
+  CHECK_CONTIG(series); CHECK_CONTIG(ts); CHECK_CONTIG(fields);
+  TORCH_CHECK(series.scalar_type() == torch::kInt32);
+  TORCH_CHECK(ts.scalar_type() == torch::kInt64);
+  TORCH_CHECK(fields.scalar_type() == torch::kFloat64);
+  TORCH_CHECK(fields.dim() == 2);
+  const int64_t n = ts.numel();
+  const int64_t nf = fields.size(0);
+  TORCH_CHECK(series.numel() == n);
+  TORCH_CHECK(fields.size(1) == n, "fields must be [nf, n]");
+  auto opts_f64 = ts.options().dtype(torch::kFloat64);
+  if (n == 0)
+    return {torch::empty({0}, ts.options().dtype(torch::kInt64)),
+            torch::empty({nf, 0}, opts_f64)};
+  auto kidx = dedup_mark_last(series, ts).nonzero().reshape({-1});
+  const int64_t g = kidx.numel();
+  auto merged = torch::empty({nf, g}, opts_f64);
+  if (nf == 0) return {kidx, merged};
+  auto stream = at::cuda::getCurrentHIPStream().stream();
+  gdb_hip::launch_merge_last_non_null(
+      kidx.data_ptr<int64_t>(), g, fields.data_ptr<double>(), n, (int)nf,
+      merged.data_ptr<double>(), stream);
+  return {kidx, merged};
 }
 
 // Accumulate per-slot max-ts keys across sources (call once per source with
@@ -607,6 +641,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("ts"), py::arg("vals"), py::arg("block"), py::arg("pack_ts"));
   m.def("filter_series_time", &filter_series_time, "series/time filter mask");
   m.def("dedup_mark_last", &dedup_mark_last, "last-row dedup marker");
+  m.def("merge_last_non_null", &merge_last_non_null,
+        "last_non_null merge: (group-last rows, merged fields)");
   m.def("series_last_ts", &series_last_ts, "per-slot max-ts accumulate (lastpoint)");
   m.def("series_last_row", &series_last_row, "per-slot winner row (lastpoint)");
   m.def("prom_range_eval", &prom_range_eval, "PromQL range-vector evaluator");

@@ -9,6 +9,8 @@
 //    over all selected fields.
 //  - filter_series_time_kernel : K1/K2 producing a keep-mask for raw scans.
 //  - dedup_mark_last_kernel : K4 last_row marker on (series, ts)-sorted data.
+//  - merge_last_non_null_kernel : K4 last_non_null merge, per field the newest
+//    non-NULL value of each (series, ts) group.
 //  - quantile_{hist,pick,next,finish}_kernel : K21 exact grouped order
 //    statistics by radix-histogram selection over bucket cells.
 //  - gorilla_decode_kernel / gorilla_{scale,widths,write}_kernel : K20 cold
@@ -141,6 +143,84 @@ __global__ void dedup_mark_last_kernel(
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     keep[i] = (i == n - 1) || (series[i] != series[i + 1]) || (ts[i] != ts[i + 1]);
+  }
+}
+
+// ---------------------------------------------------------------- K4 merge
+// last_non_null merge (reference read/dedup.rs LastNonNull): for group j of
+// the (series, ts, seq)-sorted input and field f, the output is the value of
+// the highest row of the group that is not NaN (NaN = NULL), or the group-last
+// row's own bits when every row is NaN. kidx[j] is the last row of group j
+// (the dedup_mark_last rows), so group j starts at kidx[j-1] + 1.
+//
+// Design: look-back, not a tile-level segmented scan. The output has one
+// element per GROUP, and almost every group has one row, so the common case
+// should read each kept element once and write it once: one lane per group
+// (coalesced over j; kidx[j] grows by one per lane there, so the field read
+// is coalesced too), the two kidx loads shared by all nf fields. A scan
+// would carry a (value, flag) pair through LDS for every input row to serve
+// the rare long group. A NULL last row first tries LNN_LOOKBACK earlier rows
+// in its own lane (short groups: partial writes of a few fields). Whatever
+// is still unresolved is taken over by the whole wave, one group at a time:
+// 64 rows per step, newest first, the newest valid lane picked with a ballot,
+// stopping at the group start. Every row of a group is read at most once per
+// field, so the pass stays O(n * nf) however long a group is.
+constexpr int LNN_LOOKBACK = 4;
+
+__global__ void __launch_bounds__(256) merge_last_non_null_kernel(
+    const int64_t* __restrict__ kidx, int64_t g,
+    const double* __restrict__ fields, int64_t field_stride, int nf,
+    double* __restrict__ out) {              // [nf, g]
+  const int lane = threadIdx.x & 63;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  // the loop bound depends on the wave's first group only: all 64 lanes stay
+  // in the loop together, which the ballots and shuffles below rely on
+  for (int64_t base = (int64_t)blockIdx.x * blockDim.x + (threadIdx.x - lane);
+       base < g; base += stride) {
+    const int64_t j = base + lane;
+    const bool active = j < g;
+    const int64_t last = active ? kidx[j] : 0;
+    const int64_t start = (active && j > 0) ? kidx[j - 1] + 1 : 0;
+    for (int f = 0; f < nf; f++) {
+      const double* __restrict__ col = fields + (int64_t)f * field_stride;
+      double v = 0.0;
+      bool need = false;
+      int64_t hi = -1;                       // next (older) row to examine
+      if (active) {
+        v = col[last];
+        if (isnan(v) && last > start) {
+          need = true;
+          hi = last - 1;
+          for (int k = 0; k < LNN_LOOKBACK && hi >= start; k++, hi--) {
+            const double w = col[hi];
+            if (!isnan(w)) { v = w; need = false; break; }
+          }
+          if (hi < start) need = false;      // group exhausted: keep the NaN
+        }
+      }
+      unsigned long long todo = __ballot(need);
+      while (todo) {
+        const int src = __ffsll(todo) - 1;
+        todo &= todo - 1;
+        const int64_t s_start = __shfl(start, src);
+        const int64_t s_hi = __shfl(hi, src);
+        double fv = 0.0;
+        bool found = false;
+        for (int64_t top = s_hi; top >= s_start; top -= 64) {
+          const int64_t r = top - lane;      // lane 0 holds the newest row
+          const bool in = r >= s_start;
+          const double w = in ? col[r] : 0.0;
+          const unsigned long long ok = __ballot(in && !isnan(w));
+          if (ok) {
+            fv = __shfl(w, __ffsll(ok) - 1);
+            found = true;
+            break;
+          }
+        }
+        if (found && lane == src) v = fv;
+      }
+      if (active) out[(int64_t)f * g + j] = v;
+    }
   }
 }
 
@@ -1048,6 +1128,13 @@ void launch_dedup_mark_last(
     hipStream_t stream) {
   hipLaunchKernelGGL(dedup_mark_last_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream,
       series, ts, n, keep);
+}
+
+void launch_merge_last_non_null(
+    const int64_t* kidx, int64_t g, const double* fields, int64_t field_stride,
+    int nf, double* out, hipStream_t stream) {
+  hipLaunchKernelGGL(merge_last_non_null_kernel, dim3(grid_for(g, 256)), dim3(256), 0, stream,
+      kidx, g, fields, field_stride, nf, out);
 }
 
 void launch_bucket_agg2(

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from greptimedb_amd.engine import sst as sst_mod
-from greptimedb_amd.ops import dedup_mark_last
+from greptimedb_amd.ops import dedup_mark_last, merge_last_non_null
 
 TRIGGER_FILE_NUM = 4
 MAX_INPUTS = 32
@@ -31,11 +31,63 @@ def pick_window_s(span_s: float) -> int:
     return 14 * 24 * 3600
 
 
+def close_over_sequences(files: dict, fids: list[str]) -> list[str] | None:
+    """Grow a picked group until merging it keeps the last_non_null
+    invariant: time-overlapping files of a last_non_null region never have
+    interleaved sequence ranges.
+
+    A merged row takes its group's highest sequence but only the fields seen
+    in the merged files. If a file outside the group overlaps the group in
+    time and its seq_max lies strictly between the group's smallest and
+    largest seq_max, the output would shadow that file's newer non-NULL
+    values with older ones (files 1, 2, 3 = cpu 1, 2, NULL: merging {1, 3}
+    gives cpu 1 at sequence 3, which then beats file 2's cpu 2). Such files
+    join the group, repeated until none is left; files of any level count.
+    Returns None when the closed group exceeds MAX_INPUTS: skip it this
+    round. LastRow regions need none of this, the highest sequence wins
+    whatever was merged first."""
+    group = list(fids)
+    while True:
+        metas = [files[f] for f in group]
+        lo = min(m["min_ts"] for m in metas)
+        hi = max(m["max_ts"] for m in metas)
+        s_lo = min(m.get("seq_max", 0) for m in metas)
+        s_hi = max(m.get("seq_max", 0) for m in metas)
+        extra = [f for f, m in files.items() if f not in group
+                 and m["min_ts"] <= hi and m["max_ts"] >= lo
+                 and s_lo < m.get("seq_max", 0) < s_hi]
+        if not extra:
+            return group
+        group.extend(extra)
+        if len(group) > MAX_INPUTS:
+            return None
+
+
 class Compactor:
     def __init__(self, trigger_file_num: int = TRIGGER_FILE_NUM):
         self.trigger = trigger_file_num
 
     def pick(self, region) -> list[list[str]]:
+        """Compaction candidates. LastRow and append regions take the
+        time-window groups as they are; a last_non_null region closes each
+        over sequence interleaving first (close_over_sequences) and skips a
+        group that grew too large, needs a file that is not resident, or
+        shares a file with a group already taken this round."""
+        groups = self._window_groups(region)
+        if region.merge_mode != "last_non_null":
+            return groups
+        files = region.manifest.files
+        out, taken = [], set()
+        for g in groups:
+            closed = close_over_sequences(files, g)
+            if closed is None or taken.intersection(closed) or \
+                    any(f not in region.sst_cache for f in closed):
+                continue
+            taken.update(closed)
+            out.append(closed)
+        return out
+
+    def _window_groups(self, region) -> list[list[str]]:
         """Group L0 file ids by time window; windows with >= trigger files
         are compaction candidates."""
         files = region.manifest.files
@@ -115,14 +167,25 @@ class Compactor:
         perm = o1[torch.argsort(se[o1], stable=True)]
         ts, se, seq = ts[perm], se[perm], seq[perm]
         fields = fields[:, perm]
-        if not region.append_mode:
-            keep = dedup_mark_last(se.contiguous(), ts.contiguous())
-            kidx = keep.nonzero(as_tuple=True)[0]
-            ts, se, seq, fields = ts[kidx], se[kidx], seq[kidx], fields[:, kidx]
-            perm = perm[kidx]
-        perm_h = perm.cpu().numpy()
-        str_cols_sorted = {sn: np.concatenate(parts)[perm_h]
-                           for sn, parts in str_parts.items()}
+        if region.merge_mode == "last_non_null":
+            from greptimedb_amd.engine.region import merge_str_last_non_null
+            kidx, fields = merge_last_non_null(se, ts, fields)
+            ts, se, seq = ts[kidx], se[kidx], seq[kidx]
+            perm_h = perm.cpu().numpy()
+            kidx_h = kidx.cpu().numpy()
+            str_cols_sorted = {
+                sn: merge_str_last_non_null(kidx_h,
+                                            np.concatenate(parts)[perm_h])
+                for sn, parts in str_parts.items()}
+        else:
+            if not region.append_mode:
+                keep = dedup_mark_last(se.contiguous(), ts.contiguous())
+                kidx = keep.nonzero(as_tuple=True)[0]
+                ts, se, seq, fields = ts[kidx], se[kidx], seq[kidx], fields[:, kidx]
+                perm = perm[kidx]
+            perm_h = perm.cpu().numpy()
+            str_cols_sorted = {sn: np.concatenate(parts)[perm_h]
+                               for sn, parts in str_parts.items()}
 
         ts_h = ts.cpu().numpy()
         se_h = se.cpu().numpy()

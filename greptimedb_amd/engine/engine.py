@@ -22,7 +22,8 @@ import numpy as np
 from greptimedb_amd.engine.region import Region
 from greptimedb_amd.engine.wal import Wal, decode_batch, encode_batch
 from greptimedb_amd.models.schema import TableSchema, region_id as make_region_id
-from greptimedb_amd.utils.errors import TableAlreadyExists, TableNotFound
+from greptimedb_amd.utils.errors import (InvalidArguments, TableAlreadyExists,
+                                         TableNotFound)
 
 
 @dataclass
@@ -45,11 +46,36 @@ class EngineConfig:
                                         # (reference WriteBufferManagerImpl)
 
 
+MERGE_MODES = ("last_row", "last_non_null")
+
+
+def check_merge_mode(schema, append_mode: bool, merge_mode: str) -> None:
+    """Validate a table's merge_mode (reference: mito2 MergeMode region
+    option; it rejects the append_mode combination the same way)."""
+    if merge_mode not in MERGE_MODES:
+        raise InvalidArguments(
+            f"invalid merge_mode {merge_mode!r}: expected 'last_row' or "
+            "'last_non_null'")
+    if merge_mode != "last_non_null":
+        return
+    if append_mode:
+        raise InvalidArguments(
+            "merge_mode 'last_non_null' cannot be combined with "
+            "append_mode 'true': append tables keep every row")
+    if any(c.dtype.is_string_like and c.fulltext
+           for c in schema.field_columns):
+        raise InvalidArguments(
+            "merge_mode 'last_non_null' is not supported on a table with a "
+            "FULLTEXT column: merged scan sources cannot keep per-segment "
+            "posting row numbers")
+
+
 @dataclass
 class TableState:
     schema: TableSchema
     regions: list = field(default_factory=list)
     append_mode: bool = False
+    merge_mode: str = "last_row"   # or "last_non_null" (MERGE_MODES)
     rule: object = None   # cached PartitionRule (parallel/partition.py)
     # (copy of `regions`, the same in lock order, their ids): what the
     # fused write path needs per batch, rebuilt when `regions` changes
@@ -99,12 +125,16 @@ class MitoEngine:
         self.schemas = set(cat.get("schemas", []))
         for td in cat["tables"]:
             schema = TableSchema.from_dict(td["schema"])
-            st = TableState(schema=schema, append_mode=td["append_mode"])
+            # catalogs written before merge_mode existed have no key
+            merge_mode = td.get("merge_mode", "last_row")
+            st = TableState(schema=schema, append_mode=td["append_mode"],
+                            merge_mode=merge_mode)
             for rn in range(td["n_regions"]):
                 rid = make_region_id(schema.table_id, rn)
                 rdir = os.path.join(self.config.data_dir, "region", str(rid))
                 st.regions.append(Region(rid, schema, rdir, device=self.config.device,
-                                         append_mode=td["append_mode"]))
+                                         append_mode=td["append_mode"],
+                                         merge_mode=merge_mode))
             self.tables[schema.name] = st
 
     def _save_catalog(self):
@@ -117,6 +147,7 @@ class MitoEngine:
                     "schema": st.schema.to_dict(),
                     "n_regions": len(st.regions),
                     "append_mode": st.append_mode,
+                    "merge_mode": st.merge_mode,
                 }
                 for st in self.tables.values()
             ],
@@ -127,11 +158,13 @@ class MitoEngine:
         os.rename(tmp, self._catalog_path)
 
     def create_table(self, schema: TableSchema, n_regions: int | None = None,
-                     append_mode: bool = False, if_not_exists: bool = False) -> TableState:
+                     append_mode: bool = False, if_not_exists: bool = False,
+                     merge_mode: str = "last_row") -> TableState:
+        check_merge_mode(schema, append_mode, merge_mode)
         with self._ddl_lock:
             existed = schema.name in self.tables
             st = self._create_table_locked(schema, n_regions, append_mode,
-                                           if_not_exists)
+                                           if_not_exists, merge_mode)
         if not existed and self.config.record_events:
             from greptimedb_amd.utils.events import EVENTS_TABLE, recorder_of
             if schema.name != EVENTS_TABLE:
@@ -140,7 +173,7 @@ class MitoEngine:
         return st
 
     def _create_table_locked(self, schema, n_regions, append_mode,
-                             if_not_exists) -> TableState:
+                             if_not_exists, merge_mode="last_row") -> TableState:
         if schema.name in self.tables:
             if if_not_exists:
                 return self.tables[schema.name]
@@ -149,12 +182,14 @@ class MitoEngine:
             schema.table_id = self.next_table_id
         self.next_table_id = max(self.next_table_id, schema.table_id) + 1
         n_regions = n_regions or self.config.default_regions
-        st = TableState(schema=schema, append_mode=append_mode)
+        st = TableState(schema=schema, append_mode=append_mode,
+                        merge_mode=merge_mode)
         for rn in range(n_regions):
             rid = make_region_id(schema.table_id, rn)
             rdir = os.path.join(self.config.data_dir, "region", str(rid))
             st.regions.append(Region(rid, schema, rdir, device=self.config.device,
-                                     append_mode=append_mode))
+                                     append_mode=append_mode,
+                                     merge_mode=merge_mode))
         self.tables[schema.name] = st
         self._save_catalog()
         return st

@@ -21,7 +21,7 @@ from greptimedb_amd.engine.manifest import Manifest
 from greptimedb_amd.engine.memtable import Memtable
 from greptimedb_amd.engine.series import SeriesIndex
 from greptimedb_amd.models.schema import TableSchema
-from greptimedb_amd.ops import dedup_mark_last
+from greptimedb_amd.ops import dedup_mark_last, merge_last_non_null
 
 
 class ScanSource:
@@ -44,14 +44,32 @@ class ScanSource:
         self.text_probe = text_probe
 
 
+def merge_str_last_non_null(kidx_h: np.ndarray, arr: np.ndarray) -> np.ndarray:
+    """Host half of the last_non_null merge for one string column: `arr`
+    is (series, ts, seq)-sorted, `kidx_h` the group-last rows; each group
+    yields its newest non-None value, or None when it has none."""
+    if len(kidx_h) == 0:
+        return arr[:0]
+    starts = np.concatenate(([0], kidx_h[:-1] + 1))
+    valid = np.fromiter((v is not None for v in arr), dtype=bool,
+                        count=len(arr))
+    cand = np.where(valid, np.arange(len(arr), dtype=np.int64), -1)
+    newest = np.maximum.reduceat(cand, starts)
+    return arr[np.where(newest >= 0, newest, kidx_h)]
+
+
 class Region:
     def __init__(self, region_id: int, schema: TableSchema, dir: str,
-                 device: str = "cpu", append_mode: bool = False):
+                 device: str = "cpu", append_mode: bool = False,
+                 merge_mode: str = "last_row"):
         self.region_id = region_id
         self.schema = schema
         self.dir = dir
         self.device = device
         self.append_mode = append_mode
+        # "last_row": the newest row of a (series, ts) group wins as a whole;
+        # "last_non_null": each field keeps its newest non-NULL value
+        self.merge_mode = merge_mode
         self.field_names = [c.name for c in schema.field_columns
                             if not c.dtype.is_string_like]
         # string fields (log columns): host-side values; fulltext index only
@@ -345,7 +363,13 @@ class Region:
             entry = (mem, n, mem_postings, mem_base)
             self.flushing.append(entry)
         ts, se, fields, perm = mem.sorted_view()
-        if not self.append_mode:
+        kidx_h = None
+        if self.merge_mode == "last_non_null":
+            sorted_perm_h = perm.cpu().numpy()
+            kidx, fields = merge_last_non_null(se, ts, fields)
+            ts, se, perm = ts[kidx], se[kidx], perm[kidx]
+            kidx_h = kidx.cpu().numpy()
+        elif not self.append_mode:
             keep = dedup_mark_last(se, ts)
             idx = keep.nonzero(as_tuple=True)[0]
             ts, se, fields, perm = ts[idx], se[idx], fields[:, idx], perm[idx]
@@ -358,7 +382,11 @@ class Region:
         str_cols_sorted: dict[str, np.ndarray] = {}
         text_index = {}
         for name, col in mem.str_cols.items():
-            arr = np.array(col[: n], dtype=object)[perm_h]
+            if kidx_h is not None:
+                arr = merge_str_last_non_null(
+                    kidx_h, np.array(col[: n], dtype=object)[sorted_perm_h])
+            else:
+                arr = np.array(col[: n], dtype=object)[perm_h]
             str_cols_sorted[name] = arr
             ft = self.text_cols.get(name)
             if ft is not None:
@@ -473,14 +501,21 @@ class Region:
         cache batches (time-pruned, reference scan_region.rs:887), then
         memtables being flushed, then the active memtable. Everything is
         snapshotted under the region lock so a concurrent flush can neither
-        hide rows nor mutate the dict mid-iteration."""
+        hide rows nor mutate the dict mid-iteration.
+
+        A last_non_null region answers with its merged view instead: one
+        (series, ts)-unique source (see _merged_source), so every consumer's
+        own LastRow dedup finds nothing left to drop."""
         out = []
+        seqs = []     # per source: seq tensor, int base of row 0, or None
         device = self.device
         with self.lock:
             batches = list(self.sst_cache.values())
             flushing = list(self.flushing)
             mem = self.memtable
             n = mem.len
+            mem_base = self.mem_base
+            fnames = list(self.field_names)
         for batch in batches:
             if ts_lo is not None and batch.max_ts < ts_lo:
                 continue
@@ -507,12 +542,81 @@ class Region:
                                   sorted=True,
                                   str_cols=getattr(batch, "str_cols", {}),
                                   text_probe=make_probe(batch)))
-        for fmem, fn_rows, fpostings, _base in flushing:
-            out.extend(self._mem_source(fmem, fn_rows, ts_lo, ts_hi,
-                                        postings=fpostings))
+            seqs.append(batch.seq)
+        n_sst = len(out)
+        for fmem, fn_rows, fpostings, fbase in flushing:
+            src = self._mem_source(fmem, fn_rows, ts_lo, ts_hi,
+                                   postings=fpostings)
+            out.extend(src)
+            seqs.extend([fbase] * len(src))
         if n > 0:
-            out.extend(self._mem_source(mem, n, ts_lo, ts_hi))
+            src = self._mem_source(mem, n, ts_lo, ts_hi)
+            out.extend(src)
+            seqs.extend([mem_base] * len(src))
+        if self.merge_mode == "last_non_null" and out and \
+                not (len(out) == 1 and n_sst == 1):
+            return [self._merged_source(out, seqs, fnames)]
         return out
+
+    def _merged_source(self, sources, seqs, fnames):
+        """last_non_null read path: gather the pruned sources, sort by
+        (series, ts, seq) and merge each (series, ts) group field by field.
+        A lone SST batch never gets here (flush and compaction leave it
+        group-unique). `seqs[i]` orders source i's rows: an SST's seq tensor,
+        a memtable's row-0 sequence, or None for a batch without sequences,
+        which gets file-order synthetic ones as compaction does. Nothing is
+        cached: every multi-source query re-merges its time range."""
+        device = self.device
+        total = sum(s.n for s in sources)
+        fields = torch.full((len(fnames), total), float("nan"),
+                            dtype=torch.float64, device=device)
+        seq_parts, synth_base, off = [], 0, 0
+        synth = any(q is None for q in seqs)
+        for s, q in zip(sources, seqs):
+            for fi, fn in enumerate(fnames):
+                pos = s.field_pos.get(fn)
+                if pos is not None and pos < s.fields.shape[0]:
+                    fields[fi, off:off + s.n] = s.fields[pos][: s.n]
+            if q is None:
+                q = torch.arange(synth_base, synth_base + s.n,
+                                 dtype=torch.int64, device=device)
+                synth_base += s.n
+            elif isinstance(q, int):
+                q = torch.arange(q, q + s.n, dtype=torch.int64, device=device)
+            else:
+                q = q.to(torch.int64)
+                if synth and s.n:
+                    synth_base = max(synth_base, int(q.max().item()) + 1)
+            seq_parts.append(q)
+            off += s.n
+        ts = torch.cat([s.ts[: s.n] for s in sources])
+        se = torch.cat([s.series[: s.n].to(torch.int32) for s in sources])
+        seq = torch.cat(seq_parts)
+        o0 = torch.argsort(seq, stable=True)
+        o1 = o0[torch.argsort(ts[o0], stable=True)]
+        perm = o1[torch.argsort(se[o1], stable=True)]
+        ts, se = ts[perm], se[perm]
+        kidx, merged = merge_last_non_null(se, ts, fields[:, perm])
+        str_names = []
+        for s in sources:
+            str_names.extend(k for k in s.str_cols if k not in str_names)
+        str_cols = {}
+        if str_names:
+            perm_h = perm.cpu().numpy()
+            kidx_h = kidx.cpu().numpy()
+            for name in str_names:
+                parts = []
+                for s in sources:
+                    col = s.str_cols.get(name)
+                    parts.append(np.full(s.n, None, dtype=object)
+                                 if col is None else
+                                 np.array(col[: s.n], dtype=object))
+                str_cols[name] = merge_str_last_non_null(
+                    kidx_h, np.concatenate(parts)[perm_h])
+        return ScanSource(ts[kidx].contiguous(), se[kidx].contiguous(),
+                          merged, int(kidx.numel()),
+                          {fn: i for i, fn in enumerate(fnames)},
+                          sorted=True, str_cols=str_cols, text_probe=None)
 
     def _mem_source(self, mem, n, ts_lo, ts_hi, postings=None):
         """Build the ScanSource for one (active or flushing) memtable;

@@ -35,7 +35,8 @@ def repartition_table(engine, name: str, n_new: int) -> int:
     for rn in range(n_new):
         rid = make_region_id(schema.table_id, rn)
         new_regions.append(Region(rid, schema, os.path.join(staging_base, str(rid)),
-                                  device=device, append_mode=st.append_mode))
+                                  device=device, append_mode=st.append_mode,
+                                  merge_mode=st.merge_mode))
     moved = 0
     for old in st.regions:
         ncodes = len(old.series)
@@ -114,7 +115,8 @@ def repartition_table(engine, name: str, n_new: int) -> int:
         Region(make_region_id(schema.table_id, rn), schema,
                os.path.join(engine.config.data_dir, "region",
                             str(make_region_id(schema.table_id, rn))),
-               device=device, append_mode=st.append_mode)
+               device=device, append_mode=st.append_mode,
+               merge_mode=st.merge_mode)
         for rn in range(n_new)
     ]
     # all pre-repartition data is durable in the new SSTs: advance

@@ -64,6 +64,8 @@ class FollowerReplica:
                 continue
             self.engine.create_table(schema, n_regions=td["n_regions"],
                                      append_mode=td["append_mode"],
+                                     merge_mode=td.get("merge_mode",
+                                                       "last_row"),
                                      if_not_exists=True)
         self.engine.next_table_id = max(self.engine.next_table_id,
                                         cat["next_table_id"])

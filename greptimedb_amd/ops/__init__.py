@@ -14,6 +14,7 @@ from greptimedb_amd.ops.kernels import (  # noqa: F401
     gorilla_encode,
     grouped_quantile,
     hip_ops_available,
+    merge_last_non_null,
     prom_range_eval,
     quantile_lerp,
     series_last,

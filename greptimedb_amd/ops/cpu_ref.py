@@ -332,6 +332,37 @@ def dedup_mark_last(series, ts):
     return keep
 
 
+def merge_last_non_null(series, ts, fields):
+    """last_non_null merge over (series, ts, seq)-sorted rows →
+    (kidx i64[g], merged f64[nf, g]). kidx are the group-last rows
+    (dedup_mark_last(...).nonzero()); merged[f, j] is the value of the
+    highest row of group j whose fields[f] is not NaN (NaN = NULL), or the
+    group-last row's own bits when the whole group is NaN.
+
+    A running maximum of "row index where valid, group start - 1 where not"
+    gives every row the newest valid row at or before it; group starts only
+    grow, so a value carried in from an earlier group is always below the
+    current group's start and reads as "none"."""
+    n = ts.numel()
+    nf = fields.shape[0]
+    if n == 0:
+        return (torch.zeros(0, dtype=torch.int64),
+                torch.zeros((nf, 0), dtype=torch.float64))
+    kidx = dedup_mark_last(series, ts).nonzero(as_tuple=True)[0]
+    g = kidx.numel()
+    start = torch.zeros(g, dtype=torch.int64)
+    start[1:] = kidx[:-1] + 1
+    row_start = torch.repeat_interleave(start, kidx - start + 1)   # [n]
+    rows = torch.arange(n, dtype=torch.int64)
+    merged = torch.empty((nf, g), dtype=torch.float64)
+    for f in range(nf):
+        col = fields[f]
+        cand = torch.where(torch.isnan(col), row_start - 1, rows)
+        newest = torch.cummax(cand, 0).values[kidx]
+        merged[f] = col[torch.where(newest >= start, newest, kidx)]
+    return kidx, merged
+
+
 def gorilla_encode(ts, vals, block, pack_ts=True):
     """Oracle for kernels.gorilla_encode (K20): gorilla.pack is the
     specification. → (blob u8, block_off i64[B], out_off i64[B], n);

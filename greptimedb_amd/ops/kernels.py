@@ -123,6 +123,15 @@ def dedup_mark_last(series, ts):
     return cpu_ref.dedup_mark_last(series, ts)
 
 
+def merge_last_non_null(series, ts, fields):
+    """last_non_null merge of (series, ts, seq)-sorted rows →
+    (kidx i64[g], merged f64[nf, g]); see cpu_ref.merge_last_non_null."""
+    if ts.is_cuda:
+        return tuple(_require_hip().merge_last_non_null(
+            series.contiguous(), ts.contiguous(), fields.contiguous()))
+    return cpu_ref.merge_last_non_null(series, ts, fields)
+
+
 def prom_range_eval(ts, vals, seg_lo, seg_hi, T, t0, step_ms, range_ms,
                     offset_ms, param, mode):
     """PromQL window evaluator over (slot, ts)-sorted samples → [S, T]."""

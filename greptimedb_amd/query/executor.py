@@ -502,8 +502,10 @@ class Executor:
         opts = [f"  regions = {len(st.regions)}"]
         if st.append_mode:
             opts.append("  append_mode = 'true'")
+        if st.merge_mode == "last_non_null":
+            opts.append("  merge_mode = 'last_non_null'")
         for k, v in sorted(schema.options.items()):
-            if k != "partition_rule":
+            if k not in ("partition_rule", "merge_mode"):
                 opts.append(f"  {k} = '{v}'")
         part = ""
         if schema.options.get("partition_rule"):
@@ -960,6 +962,7 @@ class Executor:
             "timestamp(9)": DataType.TIMESTAMP_NS, "datetime": DataType.TIMESTAMP_MS,
             "json": DataType.JSON,
         }
+        merge_mode = str(c.options.get("merge_mode", "last_row")).lower()
         cols = []
         for i, (name, typ, opts) in enumerate(c.columns):
             tl = typ.lower()
@@ -980,8 +983,11 @@ class Executor:
                    else SemanticType.FIELD)
             # string FIELD columns default to fulltext-indexed (observability
             # default; opt out via the column-less declaration in stores)
+            # a last_non_null table cannot carry a fulltext index, so there
+            # only an explicit FULLTEXT asks for one (and is rejected below)
             ft = opts.get("fulltext",
-                          t.is_string_like and sem == SemanticType.FIELD)
+                          t.is_string_like and sem == SemanticType.FIELD
+                          and merge_mode != "last_non_null")
             cols.append(ColumnSchema(name, t, sem, i,
                                      nullable=opts.get("nullable", True),
                                      fulltext=bool(ft)))
@@ -1002,7 +1008,8 @@ class Executor:
             n_regions = rule.n_regions
         append = str(c.options.get("append_mode", "false")).lower() == "true"
         self.engine.create_table(schema, n_regions=n_regions,
-                                 append_mode=append, if_not_exists=c.if_not_exists)
+                                 append_mode=append, if_not_exists=c.if_not_exists,
+                                 merge_mode=merge_mode)
         return QueryResult(["status"], [["ok"]])
 
     def _exec_create_external(self, c: ast.CreateTable) -> QueryResult:
