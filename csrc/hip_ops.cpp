@@ -9,79 +9,41 @@
 #include <tuple>
 #include <vector>
 
-#include "scatter_packed.h"
+#include "kernels.h"
 
-namespace gdb_hip {
-void launch_ts_bucket_agg(
-    const int64_t*, const int32_t*, const double*, int64_t, const int32_t*, int,
-    const int32_t*, int, int64_t, int64_t, int64_t, int64_t, int, int, int64_t,
-    double*, unsigned long long*, unsigned long long*, unsigned long long*,
-    unsigned long long*, hipStream_t);
-void launch_decode_minmax(
-    const unsigned long long*, const unsigned long long*, const unsigned long long*,
-    double*, double*, int64_t, hipStream_t);
-void launch_filter_series_time(
-    const int64_t*, const int32_t*, const int32_t*, int, int64_t, int64_t,
-    int64_t, bool*, hipStream_t);
-void launch_dedup_mark_last(const int32_t*, const int64_t*, int64_t, bool*, hipStream_t);
-void launch_merge_last_non_null(const int64_t*, int64_t, const double*, int64_t,
-                                int, double*, hipStream_t);
-void launch_bucket_agg2(
-    const int64_t*, const int32_t*, const double*, int64_t, const int32_t*, int,
-    const int32_t*, int, int64_t, int64_t, int64_t, int64_t, int, int, int64_t,
-    int32_t*, double*, unsigned long long*, unsigned long long*,
-    unsigned long long*, unsigned long long*, hipStream_t);
-void launch_series_last(
-    const int64_t*, const int32_t*, const int32_t*, int, int64_t, int64_t,
-    int64_t, unsigned long long*, hipStream_t);
-void launch_series_last_row(
-    const int64_t*, const int32_t*, const int32_t*, int, int64_t, int64_t,
-    int64_t, const unsigned long long*, unsigned long long,
-    unsigned long long*, hipStream_t);
-void launch_prom_range_eval(
-    const int64_t*, const double*, const int64_t*, const int64_t*, int, int,
-    int64_t, int64_t, int64_t, int64_t, double, int, double*, hipStream_t);
-void launch_scatter_append(
-    const int64_t*, const int32_t*, const double*, const int32_t*,
-    const int64_t*, int64_t* const*, int32_t* const*, double* const*,
-    const int64_t*, int, int64_t, hipStream_t);
-void launch_scatter_append_packed(
-    const unsigned char*, int64_t, int, const PackedRegions&, hipStream_t);
-void launch_rle_expand_indices(const int64_t*, int64_t, const uint8_t*, int,
-                               int32_t*, int64_t, hipStream_t);
-void launch_gorilla_decode(const uint8_t*, const int64_t*, const int64_t*,
-                           int64_t, int64_t*, double*, int64_t, hipStream_t);
-int gorilla_encode_max_block();
-void launch_gorilla_scale(const double*, int64_t, unsigned*, hipStream_t);
-void launch_gorilla_widths(const int64_t*, const double*, int64_t, int, int,
-                           const unsigned*, uint8_t*, int64_t*, int64_t,
-                           hipStream_t);
-void launch_gorilla_write(const int64_t*, const double*, int64_t, int,
-                          const unsigned*, const uint8_t*, const int64_t*,
-                          uint8_t*, int64_t, hipStream_t);
-void launch_bucket_cells(
-    const int64_t*, const int32_t*, const int32_t*, int, int64_t, int64_t,
-    int64_t, int64_t, int, int64_t, int32_t*, hipStream_t);
-void launch_quantile_hist(
-    const int32_t*, const double*, int64_t, const int32_t*, int, const int32_t*,
-    int, int64_t, int, int, int, const unsigned long long*, unsigned int*,
-    hipStream_t);
-void launch_quantile_pick(
-    unsigned int*, const double*, int, int64_t, int, unsigned long long*,
-    int64_t*, int64_t*, int64_t*, hipStream_t);
-void launch_quantile_next(
-    const int32_t*, const double*, int64_t, const int32_t*, int, const int32_t*,
-    int, int64_t, int, int, const unsigned long long*, unsigned long long*,
-    unsigned long long*, hipStream_t);
-void launch_quantile_finish(
-    const unsigned long long*, const int64_t*, const int64_t*,
-    const unsigned long long*, const unsigned long long*, int64_t, double*,
-    double*, hipStream_t);
-void quantile_launch_config(int64_t out[3]);
-}  // namespace gdb_hip
+// The one argument check of every op below: `t` must be on the GPU and on the
+// device of the op's first tensor `first`, of dtype `dt`, and contiguous.
+// Like every check in this file it looks at metadata only: it reads no device
+// memory and does not synchronize, so an invalid call raises before anything
+// is queued and a valid call costs nothing on the device.
+static void check_arg(const torch::Tensor& t, const char* name,
+                      torch::ScalarType dt, const torch::Tensor& first) {
+  TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor");
+  TORCH_CHECK(t.device() == first.device(), name, " is on ", t.device(),
+              ", the op's first tensor on ", first.device());
+  TORCH_CHECK(t.scalar_type() == dt, name, " must be ", dt, ", got ",
+              t.scalar_type());
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+}
 
-#define CHECK_GPU(x) TORCH_CHECK(x.is_cuda(), #x " must be on GPU")
-#define CHECK_CONTIG(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
+// The 5 raw accumulators of ts_bucket_agg: sum f64, cnt, min keys, max keys
+// i64, each [nf, n_slots, n_buckets], and rows i64[n_slots, n_buckets].
+static void check_acc(const std::vector<torch::Tensor>& acc,
+                      const torch::Tensor& first) {
+  TORCH_CHECK(acc.size() == 5, "acc must be the 5 raw accumulators");
+  check_arg(acc[0], "acc[0] (sum)", torch::kFloat64, first);
+  check_arg(acc[1], "acc[1] (cnt)", torch::kInt64, first);
+  check_arg(acc[2], "acc[2] (min keys)", torch::kInt64, first);
+  check_arg(acc[3], "acc[3] (max keys)", torch::kInt64, first);
+  check_arg(acc[4], "acc[4] (rows)", torch::kInt64, first);
+  TORCH_CHECK(acc[0].dim() == 3 && acc[4].dim() == 2 &&
+              acc[1].sizes() == acc[0].sizes() &&
+              acc[2].sizes() == acc[0].sizes() &&
+              acc[3].sizes() == acc[0].sizes() &&
+              acc[4].sizes() == acc[0].sizes().slice(1),
+              "acc must be four [nf, n_slots, n_buckets] tensors and one "
+              "[n_slots, n_buckets]");
+}
 
 // Fused filter + time-bucket aggregate (K1+K2+K5).
 // ts: i64[n] (ms), series: i32[n], fields: f64[nf_total, field_stride]
@@ -96,24 +58,33 @@ std::vector<torch::Tensor> ts_bucket_agg(
     int64_t ts_lo, int64_t ts_hi, int64_t origin, int64_t bucket_ms,
     int64_t n_slots, int64_t n_buckets,
     std::vector<torch::Tensor> acc) {
-  CHECK_GPU(ts); CHECK_GPU(series); CHECK_GPU(fields);
-  CHECK_GPU(field_idx); CHECK_GPU(slot_lut);
-  CHECK_CONTIG(ts); CHECK_CONTIG(series); CHECK_CONTIG(fields);
-  CHECK_CONTIG(field_idx); CHECK_CONTIG(slot_lut);
-  TORCH_CHECK(ts.scalar_type() == torch::kInt64);
-  TORCH_CHECK(series.scalar_type() == torch::kInt32);
-  TORCH_CHECK(fields.scalar_type() == torch::kFloat64);
+  check_arg(ts, "ts", torch::kInt64, ts);
+  check_arg(series, "series", torch::kInt32, ts);
+  check_arg(fields, "fields", torch::kFloat64, ts);
+  check_arg(field_idx, "field_idx", torch::kInt32, ts);
+  check_arg(slot_lut, "slot_lut", torch::kInt32, ts);
   TORCH_CHECK(fields.dim() == 2);
   const int64_t n = ts.numel();
-  TORCH_CHECK(series.numel() == n);
+  TORCH_CHECK(series.numel() == n, "series and ts differ in length");
   TORCH_CHECK(fields.size(1) >= n, "fields stride shorter than rows");
-  const int nf = (int)field_idx.numel();
+  // cell ids are int32 and per-field offsets int in the kernels
+  const int64_t nf64 = field_idx.numel();
+  TORCH_CHECK(n_slots >= 0 && n_slots <= INT32_MAX && n_buckets >= 0 &&
+              n_buckets <= INT32_MAX && nf64 <= INT32_MAX &&
+              n_slots * n_buckets <= INT32_MAX &&
+              nf64 * (n_slots * n_buckets) <= INT32_MAX,
+              "nf * n_slots * n_buckets = ", nf64, " * ", n_slots, " * ",
+              n_buckets, " does not fit the kernels' int32 cell arithmetic");
+  const int nf = (int)nf64;
   auto opts_f64 = ts.options().dtype(torch::kFloat64);
   auto opts_i64 = ts.options().dtype(torch::kInt64);
-  const int64_t cells = nf * n_slots * n_buckets;
   torch::Tensor sum, cnt, rows, minmax_init_min, minmax_init_max;
   if (!acc.empty()) {
-    TORCH_CHECK(acc.size() == 5, "acc must be the 5 raw accumulators");
+    // what this op itself would have created below, on the same device
+    check_acc(acc, ts);
+    TORCH_CHECK(acc[0].size(0) == nf && acc[0].size(1) == n_slots &&
+                acc[0].size(2) == n_buckets,
+                "acc was made for another nf, n_slots or n_buckets");
     sum = acc[0]; cnt = acc[1]; minmax_init_min = acc[2];
     minmax_init_max = acc[3]; rows = acc[4];
   } else {
@@ -129,7 +100,7 @@ std::vector<torch::Tensor> ts_bucket_agg(
   if (n == 0) return {sum, cnt, minmax_init_min, minmax_init_max, rows};
   auto stream = at::cuda::getCurrentHIPStream().stream();
   auto cell = torch::empty({n}, ts.options().dtype(torch::kInt32));
-  gdb_hip::launch_bucket_agg2(
+  gdb_hip::launch_ts_bucket_agg(
       ts.data_ptr<int64_t>(), series.data_ptr<int32_t>(), fields.data_ptr<double>(),
       fields.size(1), field_idx.data_ptr<int32_t>(), nf,
       slot_lut.data_ptr<int32_t>(), (int)slot_lut.numel(),
@@ -147,7 +118,8 @@ std::vector<torch::Tensor> ts_bucket_agg(
 // Decode raw accumulators (min/max u64 keys) → final (sum, cnt, min f64,
 // max f64, rows). Call once after the last ts_bucket_agg of a scan.
 std::vector<torch::Tensor> ts_bucket_agg_finish(std::vector<torch::Tensor> acc) {
-  TORCH_CHECK(acc.size() == 5);
+  TORCH_CHECK(!acc.empty(), "acc must be the 5 raw accumulators");
+  check_acc(acc, acc[0]);
   auto sum = acc[0];
   auto cnt = acc[1];
   const int64_t cells = cnt.numel();
@@ -165,13 +137,16 @@ std::vector<torch::Tensor> ts_bucket_agg_finish(std::vector<torch::Tensor> acc) 
 torch::Tensor filter_series_time(
     torch::Tensor ts, torch::Tensor series, torch::Tensor slot_lut,
     int64_t ts_lo, int64_t ts_hi) {
-  CHECK_GPU(ts); CHECK_CONTIG(ts);
+  check_arg(ts, "ts", torch::kInt64, ts);
+  check_arg(series, "series", torch::kInt32, ts);
   const int64_t n = ts.numel();
   auto keep = torch::empty({n}, ts.options().dtype(torch::kBool));
+  // an empty LUT selects every series; the kernel then never reads `series`
   const int32_t* lut = nullptr;
   int lut_size = 0;
   if (slot_lut.numel() > 0) {
-    CHECK_GPU(slot_lut); CHECK_CONTIG(slot_lut);
+    check_arg(slot_lut, "slot_lut", torch::kInt32, ts);
+    TORCH_CHECK(series.numel() == n, "series and ts differ in length");
     lut = slot_lut.data_ptr<int32_t>();
     lut_size = (int)slot_lut.numel();
   }
@@ -183,8 +158,10 @@ torch::Tensor filter_series_time(
 }
 
 torch::Tensor dedup_mark_last(torch::Tensor series, torch::Tensor ts) {
-  CHECK_GPU(series); CHECK_GPU(ts); CHECK_CONTIG(series); CHECK_CONTIG(ts);
+  check_arg(series, "series", torch::kInt32, series);
+  check_arg(ts, "ts", torch::kInt64, series);
   const int64_t n = ts.numel();
+  TORCH_CHECK(series.numel() == n, "series and ts differ in length");
   auto keep = torch::empty({n}, ts.options().dtype(torch::kBool));
   auto stream = at::cuda::getCurrentHIPStream().stream();
   gdb_hip::launch_dedup_mark_last(
@@ -200,11 +177,9 @@ torch::Tensor dedup_mark_last(torch::Tensor series, torch::Tensor ts) {
 // LastRow path's own nonzero does.
 std::tuple<torch::Tensor, torch::Tensor> merge_last_non_null(
     torch::Tensor series, torch::Tensor ts, torch::Tensor fields) {
-  CHECK_GPU(series); CHECK_GPU(ts); CHECK_GPU(fields);
-  CHECK_CONTIG(series); CHECK_CONTIG(ts); CHECK_CONTIG(fields);
-  TORCH_CHECK(series.scalar_type() == torch::kInt32);
-  TORCH_CHECK(ts.scalar_type() == torch::kInt64);
-  TORCH_CHECK(fields.scalar_type() == torch::kFloat64);
+  check_arg(series, "series", torch::kInt32, series);
+  check_arg(ts, "ts", torch::kInt64, series);
+  check_arg(fields, "fields", torch::kFloat64, series);
   TORCH_CHECK(fields.dim() == 2);
   const int64_t n = ts.numel();
   const int64_t nf = fields.size(0);
@@ -225,11 +200,25 @@ std::tuple<torch::Tensor, torch::Tensor> merge_last_non_null(
   return {kidx, merged};
 }
 
+// Arguments the two lastpoint ops share. best_key and best_row are indexed by
+// the slots that slot_lut holds on the device, so their length against the
+// LUT's values stays the caller's contract (ops.series_last sizes them).
+static void check_lastpoint_args(const torch::Tensor& ts,
+                                 const torch::Tensor& series,
+                                 const torch::Tensor& slot_lut,
+                                 const torch::Tensor& best_key) {
+  check_arg(ts, "ts", torch::kInt64, ts);
+  check_arg(series, "series", torch::kInt32, ts);
+  check_arg(slot_lut, "slot_lut", torch::kInt32, ts);
+  check_arg(best_key, "best_key", torch::kInt64, ts);
+  TORCH_CHECK(series.numel() == ts.numel(), "series and ts differ in length");
+}
+
 // Accumulate per-slot max-ts keys across sources (call once per source with
 // a shared best_key tensor, int64 viewed as u64 keys, init 0).
 void series_last_ts(torch::Tensor ts, torch::Tensor series, torch::Tensor slot_lut,
                     int64_t ts_lo, int64_t ts_hi, torch::Tensor best_key) {
-  CHECK_GPU(ts); CHECK_CONTIG(ts); CHECK_GPU(best_key); CHECK_CONTIG(best_key);
+  check_lastpoint_args(ts, series, slot_lut, best_key);
   auto stream = at::cuda::getCurrentHIPStream().stream();
   gdb_hip::launch_series_last(
       ts.data_ptr<int64_t>(), series.data_ptr<int32_t>(),
@@ -242,7 +231,8 @@ void series_last_ts(torch::Tensor ts, torch::Tensor series, torch::Tensor slot_l
 void series_last_row(torch::Tensor ts, torch::Tensor series, torch::Tensor slot_lut,
                      int64_t ts_lo, int64_t ts_hi, torch::Tensor best_key,
                      int64_t src_tag, torch::Tensor best_row) {
-  CHECK_GPU(ts); CHECK_CONTIG(ts);
+  check_lastpoint_args(ts, series, slot_lut, best_key);
+  check_arg(best_row, "best_row", torch::kInt64, ts);
   auto stream = at::cuda::getCurrentHIPStream().stream();
   gdb_hip::launch_series_last_row(
       ts.data_ptr<int64_t>(), series.data_ptr<int32_t>(),
@@ -259,8 +249,15 @@ torch::Tensor prom_range_eval(
     torch::Tensor ts, torch::Tensor vals, torch::Tensor seg_lo, torch::Tensor seg_hi,
     int64_t T, int64_t t0, int64_t step_ms, int64_t range_ms, int64_t offset_ms,
     double param, int64_t mode) {
-  CHECK_GPU(ts); CHECK_CONTIG(ts); CHECK_GPU(vals); CHECK_CONTIG(vals);
-  CHECK_GPU(seg_lo); CHECK_CONTIG(seg_lo); CHECK_GPU(seg_hi); CHECK_CONTIG(seg_hi);
+  check_arg(ts, "ts", torch::kInt64, ts);
+  check_arg(vals, "vals", torch::kFloat64, ts);
+  check_arg(seg_lo, "seg_lo", torch::kInt64, ts);
+  check_arg(seg_hi, "seg_hi", torch::kInt64, ts);
+  TORCH_CHECK(vals.numel() == ts.numel(), "vals and ts differ in length");
+  TORCH_CHECK(seg_hi.numel() == seg_lo.numel(),
+              "seg_lo and seg_hi differ in length");
+  // the segment bounds themselves live on the device: 0 <= seg_lo <= seg_hi
+  // <= ts.numel() is the caller's contract
   const int S = (int)seg_lo.numel();
   auto out = torch::empty({S, T}, vals.options());
   auto stream = at::cuda::getCurrentHIPStream().stream();
@@ -279,14 +276,32 @@ void scatter_append(
     torch::Tensor region_of, torch::Tensor dst_off,
     std::vector<torch::Tensor> dst_ts, std::vector<torch::Tensor> dst_se,
     std::vector<torch::Tensor> dst_fields) {
-  CHECK_GPU(ts); CHECK_CONTIG(ts); CHECK_GPU(fields); CHECK_CONTIG(fields);
-  CHECK_GPU(region_of); CHECK_CONTIG(region_of);
-  CHECK_GPU(dst_off); CHECK_CONTIG(dst_off);
+  check_arg(ts, "ts", torch::kInt64, ts);
+  check_arg(series, "series", torch::kInt32, ts);
+  check_arg(fields, "fields", torch::kFloat64, ts);
+  check_arg(region_of, "region_of", torch::kInt32, ts);
+  check_arg(dst_off, "dst_off", torch::kInt64, ts);
   const int64_t n = ts.numel();
+  TORCH_CHECK(fields.dim() == 2 && fields.size(1) == n, "fields must be [nf, n]");
+  TORCH_CHECK(series.numel() == n && region_of.numel() == n &&
+              dst_off.numel() == n,
+              "series, region_of and dst_off must have one element per row");
   const int nf = (int)fields.size(0);
   const int R = (int)dst_ts.size();
+  TORCH_CHECK(dst_se.size() == dst_ts.size() &&
+              dst_fields.size() == dst_ts.size(),
+              "per-region lists differ in length");
+  // The VALUES of region_of and dst_off live on the device and are not read
+  // back: 0 <= region_of[i] < R and a dst_off[i] inside region region_of[i]
+  // are the caller's contract (scatter_append_packed checks them on the host
+  // because its batch starts there).
   std::vector<int64_t> hptrs(R * 3 + R);
   for (int r = 0; r < R; r++) {
+    check_arg(dst_ts[r], "dst_ts[r]", torch::kInt64, ts);
+    check_arg(dst_se[r], "dst_se[r]", torch::kInt32, ts);
+    check_arg(dst_fields[r], "dst_fields[r]", torch::kFloat64, ts);
+    TORCH_CHECK(dst_fields[r].dim() == 2 && dst_fields[r].size(0) >= nf,
+                "region ", r, " has fewer field rows than the batch");
     hptrs[r] = (int64_t)dst_ts[r].data_ptr<int64_t>();
     hptrs[R + r] = (int64_t)dst_se[r].data_ptr<int32_t>();
     hptrs[2 * R + r] = (int64_t)dst_fields[r].data_ptr<double>();
@@ -320,9 +335,10 @@ void scatter_append_packed(
     std::vector<torch::Tensor> dst_se, std::vector<torch::Tensor> dst_fields) {
   TORCH_CHECK(!stage_pinned.is_cuda() && stage_pinned.is_pinned(),
               "stage_pinned must be pinned host memory");
-  CHECK_GPU(stage_dev); CHECK_CONTIG(stage_pinned); CHECK_CONTIG(stage_dev);
-  TORCH_CHECK(stage_pinned.scalar_type() == torch::kUInt8 &&
-              stage_dev.scalar_type() == torch::kUInt8, "stage blocks are uint8");
+  check_arg(stage_dev, "stage_dev", torch::kUInt8, stage_dev);
+  TORCH_CHECK(stage_pinned.is_contiguous() &&
+              stage_pinned.scalar_type() == torch::kUInt8,
+              "stage_pinned must be contiguous uint8");
   TORCH_CHECK(n >= 0 && nf >= 0);
   if (n == 0) return;
   const int R = (int)dst_ts.size();
@@ -343,8 +359,9 @@ void scatter_append_packed(
     regs.stride[r] = 0; regs.base[r] = 0;
   }
   for (int r = 0; r < R; r++) {
-    CHECK_GPU(dst_ts[r]); CHECK_GPU(dst_se[r]); CHECK_GPU(dst_fields[r]);
-    CHECK_CONTIG(dst_ts[r]); CHECK_CONTIG(dst_se[r]); CHECK_CONTIG(dst_fields[r]);
+    check_arg(dst_ts[r], "dst_ts[r]", torch::kInt64, stage_dev);
+    check_arg(dst_se[r], "dst_se[r]", torch::kInt32, stage_dev);
+    check_arg(dst_fields[r], "dst_fields[r]", torch::kFloat64, stage_dev);
     TORCH_CHECK(dst_fields[r].dim() == 2 && dst_fields[r].size(0) >= nf,
                 "region ", r, " has fewer field rows than the batch");
     TORCH_CHECK(bases[r] >= 0);
@@ -390,7 +407,13 @@ void scatter_append_packed(
 // (pad >= 8 bytes past the last packed bit).
 torch::Tensor rle_expand_indices(torch::Tensor runs, torch::Tensor blob,
                                  int64_t bw, int64_t n) {
-  CHECK_GPU(runs); CHECK_CONTIG(runs); CHECK_GPU(blob); CHECK_CONTIG(blob);
+  check_arg(runs, "runs", torch::kInt64, runs);
+  check_arg(blob, "blob", torch::kUInt8, runs);
+  TORCH_CHECK(runs.dim() == 2 && runs.size(1) == 5, "runs must be [R, 5]");
+  TORCH_CHECK(bw >= 1 && bw <= 32, "bw must be in [1, 32], got ", bw);
+  TORCH_CHECK(n == 0 || runs.size(0) >= 1, "no runs for ", n, " values");
+  // the run table's offsets and counts live on the device: runs that cover
+  // [0, n) and stay inside the padded blob are the caller's contract
   auto out = torch::empty({n}, blob.options().dtype(torch::kInt32));
   auto stream = at::cuda::getCurrentHIPStream().stream();
   gdb_hip::launch_rle_expand_indices(
@@ -403,8 +426,12 @@ torch::Tensor rle_expand_indices(torch::Tensor runs, torch::Tensor blob,
 std::vector<torch::Tensor> gorilla_decode(torch::Tensor blob,
                                           torch::Tensor block_off,
                                           torch::Tensor out_off, int64_t n) {
-  CHECK_GPU(blob); CHECK_CONTIG(blob);
-  CHECK_GPU(block_off); CHECK_GPU(out_off);
+  check_arg(blob, "blob", torch::kUInt8, blob);
+  check_arg(block_off, "block_off", torch::kInt64, blob);
+  check_arg(out_off, "out_off", torch::kInt64, blob);
+  TORCH_CHECK(out_off.numel() == block_off.numel(),
+              "block_off and out_off differ in length");
+  TORCH_CHECK(n == 0 || block_off.numel() >= 1, "no blocks for ", n, " values");
   auto ts = torch::empty({n}, blob.options().dtype(torch::kInt64));
   auto vals = torch::empty({n}, blob.options().dtype(torch::kFloat64));
   auto stream = at::cuda::getCurrentHIPStream().stream();
@@ -422,20 +449,17 @@ std::vector<torch::Tensor> gorilla_decode(torch::Tensor blob,
 std::vector<torch::Tensor> gorilla_encode(torch::Tensor ts,
                                           c10::optional<torch::Tensor> vals,
                                           int64_t block, bool pack_ts) {
-  CHECK_GPU(ts); CHECK_CONTIG(ts);
-  TORCH_CHECK(ts.scalar_type() == torch::kInt64, "ts must be int64");
+  check_arg(ts, "ts", torch::kInt64, ts);
   TORCH_CHECK(ts.dim() == 1, "ts must be one-dimensional");
-  TORCH_CHECK(block >= 1 && block <= gdb_hip::gorilla_encode_max_block(),
-              "gorilla_encode: block must be in [1, ",
-              gdb_hip::gorilla_encode_max_block(), "], got ", block);
+  TORCH_CHECK(block >= 1 && block <= gdb_hip::GENC_MAX_BLOCK,
+              "gorilla_encode: block must be in [1, ", gdb_hip::GENC_MAX_BLOCK,
+              "], got ", block);
   const int64_t n = ts.numel();
   const double* vals_p = nullptr;
   if (vals.has_value()) {
     const torch::Tensor& v = *vals;
-    CHECK_GPU(v); CHECK_CONTIG(v);
-    TORCH_CHECK(v.scalar_type() == torch::kFloat64, "vals must be float64");
+    check_arg(v, "vals", torch::kFloat64, ts);
     TORCH_CHECK(v.dim() == 1 && v.numel() == n, "vals must match ts in length");
-    TORCH_CHECK(v.device() == ts.device(), "ts and vals on different devices");
     vals_p = v.data_ptr<double>();
   }
   auto opts_u8 = ts.options().dtype(torch::kUInt8);
@@ -473,11 +497,9 @@ torch::Tensor bucket_cells(
     torch::Tensor ts, torch::Tensor series, torch::Tensor slot_lut,
     int64_t ts_lo, int64_t ts_hi, int64_t origin, int64_t bucket_ms,
     int64_t n_buckets) {
-  CHECK_GPU(ts); CHECK_GPU(series); CHECK_GPU(slot_lut);
-  CHECK_CONTIG(ts); CHECK_CONTIG(series); CHECK_CONTIG(slot_lut);
-  TORCH_CHECK(ts.scalar_type() == torch::kInt64);
-  TORCH_CHECK(series.scalar_type() == torch::kInt32);
-  TORCH_CHECK(slot_lut.scalar_type() == torch::kInt32);
+  check_arg(ts, "ts", torch::kInt64, ts);
+  check_arg(series, "series", torch::kInt32, ts);
+  check_arg(slot_lut, "slot_lut", torch::kInt32, ts);
   TORCH_CHECK(bucket_ms > 0 && n_buckets > 0 && n_buckets <= INT32_MAX);
   const int64_t n = ts.numel();
   TORCH_CHECK(series.numel() == n);
@@ -527,10 +549,14 @@ std::vector<torch::Tensor> grouped_quantile(
     auto& cell = std::get<0>(src);
     auto& fields = std::get<1>(src);
     auto& fidx = std::get<2>(src);
-    CHECK_GPU(cell); CHECK_GPU(fields); CHECK_GPU(fidx);
-    CHECK_CONTIG(cell); CHECK_CONTIG(fidx);
-    TORCH_CHECK(cell.scalar_type() == torch::kInt32 && cell.dim() == 1);
-    TORCH_CHECK(fidx.scalar_type() == torch::kInt32 && fidx.dim() == 1);
+    const torch::Tensor& first = std::get<0>(sources.front());
+    check_arg(cell, "cell", torch::kInt32, first);
+    check_arg(fidx, "field_idx", torch::kInt32, first);
+    TORCH_CHECK(cell.dim() == 1 && fidx.dim() == 1);
+    // fields may be a row-strided view (a memtable's used prefix), so it is
+    // the one tensor that does not go through check_arg
+    TORCH_CHECK(fields.is_cuda() && fields.device() == first.device(),
+                "fields must be a GPU tensor on the first source's device");
     TORCH_CHECK(fields.scalar_type() == torch::kFloat64 && fields.dim() == 2);
     TORCH_CHECK(fields.size(1) >= cell.numel(), "fields shorter than rows");
     TORCH_CHECK(fields.size(1) <= 1 || fields.stride(1) == 1,
@@ -540,10 +566,6 @@ std::vector<torch::Tensor> grouped_quantile(
     for (int64_t f : field_of_sel)
       TORCH_CHECK(f >= 0 && f < fidx.numel(), "field_of_sel ", f,
                   " outside field_idx of length ", fidx.numel());
-    TORCH_CHECK(fields.device() == cell.device() && fidx.device() == cell.device(),
-                "a source's tensors must share one device");
-    TORCH_CHECK(std::get<0>(sources.front()).device() == cell.device(),
-                "all sources must be on the same device");
     total_rows += (uint64_t)cell.numel();
     dev = cell.device();
   }
@@ -623,12 +645,13 @@ std::vector<torch::Tensor> grouped_quantile(
 
 // {tile rows, LDS cell capacity, grid cap} of the selection kernels.
 std::vector<int64_t> quantile_launch_config() {
-  int64_t c[3];
-  gdb_hip::quantile_launch_config(c);
-  return {c[0], c[1], c[2]};
+  return {gdb_hip::QSEL_TILE, gdb_hip::QSEL_LDS_CELLS, gdb_hip::QSEL_MAX_GRID};
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  // geometry of the bucket aggregate, for tests that build tiles at its edges
+  m.attr("AGG_TILE") = gdb_hip::AGG_TILE;
+  m.attr("LDS_CELLS") = gdb_hip::LDS_CELLS;
   m.def("ts_bucket_agg", &ts_bucket_agg, "fused filter + time-bucket aggregate",
         py::arg("ts"), py::arg("series"), py::arg("fields"), py::arg("field_idx"),
         py::arg("slot_lut"), py::arg("ts_lo"), py::arg("ts_hi"), py::arg("origin"),

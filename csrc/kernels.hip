@@ -1,18 +1,25 @@
-// CDNA4 (gfx950 / MI355X) kernels for the mito-hip scan path.
+// CDNA4 (gfx950 / MI355X) kernels for the mito-hip scan, ingest and cold-tier
+// paths. Launchers are declared in kernels.h and defined at the end of this
+// file; csrc/hip_ops.cpp binds them to torch.
 //
-// Kernel inventory (SURVEY.md §2.7 numbering):
-//  - ts_bucket_agg_kernel : fused K1 (predicate filter via series LUT) +
-//    K2 (time-range visibility) + K5 (time-bucket aggregate). One pass over
-//    the (ts, series, fields) columns computing sum/count/min/max for every
-//    requested field into [nf, n_slots, n_buckets] accumulators.
-//    Memory-bound by design: ts+series loaded once per row and amortized
-//    over all selected fields.
-//  - filter_series_time_kernel : K1/K2 producing a keep-mask for raw scans.
+// Kernel inventory (SURVEY.md §2.7 numbering), in file order:
+//  - decode_minmax_kernel : K5 finish, min/max order keys -> f64.
+//  - filter_series_time_kernel : K1/K2 keep-mask for raw scans.
 //  - dedup_mark_last_kernel : K4 last_row marker on (series, ts)-sorted data.
 //  - merge_last_non_null_kernel : K4 last_non_null merge, per field the newest
 //    non-NULL value of each (series, ts) group.
+//  - bucket_cell_coalesced_kernel + field_bucket_agg_lds_kernel : fused K1
+//    (predicate filter via series LUT) + K2 (time-range visibility) + K5
+//    (time-bucket aggregate): sum/count/min/max of every requested field
+//    into [nf, n_slots, n_buckets] accumulators, in LDS-privatized tiles.
+//  - series_last_ts_kernel / series_last_row_kernel : lastpoint, per-slot
+//    argmax(ts) with a (source, row) tie-break.
+//  - prom_range_eval_kernel : K7/K8 PromQL selector and range functions.
 //  - quantile_{hist,pick,next,finish}_kernel : K21 exact grouped order
 //    statistics by radix-histogram selection over bucket cells.
+//  - scatter_append_kernel / scatter_append_packed_kernel : K16 routed
+//    ingest batch -> region memtables.
+//  - rle_expand_indices_kernel : K11 parquet hybrid RLE/bit-packed indices.
 //  - gorilla_decode_kernel / gorilla_{scale,widths,write}_kernel : K20 cold
 //    tier, fixed-width-per-block delta codec, decoded and encoded in HBM.
 //
@@ -22,19 +29,22 @@
 //  * f64 min/max accumulate through the monotonic u64 key mapping so we can
 //    use hardware atomicMin/Max on unsigned long long (no f64 min/max atomic).
 //  * NaN field values are nulls (influx missing fields) and are skipped.
-//  * Small aggregate tables (slots*buckets) stay hot in L2/LLC; per-LDS
-//    privatization is a planned optimization once rocprof shows atomic
-//    contention (expected only for >100k groups).
+//  * Accumulators with many writers per address are privatized in LDS per
+//    row tile (bucket aggregate, quantile histograms) and flushed once per
+//    tile; a tile whose cells do not fit the LDS table uses global atomics.
 
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
-#include "scatter_packed.h"
+#include "kernels.h"
 
 #define DEV_INLINE __device__ __forceinline__
 
 namespace gdb_hip {
 
+// IEEE-754 double <-> totally-ordered u64 (sign-flip transform): key order ==
+// numeric order, so u64 atomicMin/Max order doubles and order statistics can
+// be selected bitwise.
 DEV_INLINE uint64_t f64_to_key(double d) {
   uint64_t bits = __double_as_longlong(d);
   return (int64_t)bits < 0 ? ~bits : (bits | 0x8000000000000000ULL);
@@ -45,6 +55,8 @@ DEV_INLINE double key_to_f64(uint64_t key) {
   return __longlong_as_double(bits);
 }
 
+DEV_INLINE double quiet_nan() { return __longlong_as_double(0x7FF8000000000000LL); }
+
 // Bucket index = floor((t - origin) / bucket_ms), as cpu_ref defines it.
 // C++ '/' truncates toward zero, which would fold origin-bucket_ms < t <
 // origin into bucket 0; every t < origin floors below 0 (bucket_ms > 0), so
@@ -54,48 +66,28 @@ DEV_INLINE int64_t bucket_index(int64_t t, int64_t origin, int64_t bucket_ms) {
   return d < 0 ? -1 : d / bucket_ms;
 }
 
-// ---------------------------------------------------------------- K1+K2+K5
-// fields: column-major per field: fields[f * field_stride + row]
-// out arrays: [nf, n_slots, n_buckets]
-__global__ void ts_bucket_agg_kernel(
-    const int64_t* __restrict__ ts,
-    const int32_t* __restrict__ series,
-    const double* __restrict__ fields,
-    int64_t field_stride,
-    const int32_t* __restrict__ field_idx, int nf,
-    const int32_t* __restrict__ slot_lut, int lut_size,
-    int64_t ts_lo, int64_t ts_hi, int64_t origin, int64_t bucket_ms,
-    int n_slots, int n_buckets, int64_t n,
-    double* __restrict__ out_sum,
-    unsigned long long* __restrict__ out_cnt,
-    unsigned long long* __restrict__ out_min,
-    unsigned long long* __restrict__ out_max,
-    unsigned long long* __restrict__ out_rows) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const int64_t t = ts[i];
-    if (t < ts_lo || t >= ts_hi) continue;
-    const int32_t s = series[i];
-    if (s < 0 || s >= lut_size) continue;
-    const int32_t slot = slot_lut[s];
-    if (slot < 0) continue;
-    int64_t b = bucket_index(t, origin, bucket_ms);
-    if (b < 0 || b >= n_buckets) continue;
-    const int64_t cell0 = (int64_t)slot * n_buckets + b;
-    atomicAdd(&out_rows[cell0], 1ULL);
-    for (int f = 0; f < nf; f++) {
-      const double v = fields[(int64_t)field_idx[f] * field_stride + i];
-      if (isnan(v)) continue;
-      const int64_t cell = (int64_t)f * n_slots * n_buckets + cell0;
-      atomicAdd(&out_sum[cell], v);
-      atomicAdd(&out_cnt[cell], 1ULL);
-      const uint64_t k = f64_to_key(v);
-      atomicMin(&out_min[cell], (unsigned long long)k);
-      atomicMax(&out_max[cell], (unsigned long long)k);
-    }
-  }
+// Row visibility (K1 + K2): whether row i, with timestamp t, is visible, and
+// if so its slot. Not visible: t outside [ts_lo, ts_hi), series[i] outside
+// the LUT (an empty LUT hides every row), or a negative LUT entry. series[i]
+// is read only for a row inside the time window. Only a caller whose contract
+// says so passes null_lut_is_all: a null slot_lut then selects every series
+// (slot 0) without reading series at all.
+// A bool with the slot on the side, not "slot or -1": the callers' early
+// `continue`s then compile to the branches they were when written out.
+DEV_INLINE bool visible_row(int64_t t, const int32_t* __restrict__ series,
+                            int64_t i, const int32_t* __restrict__ slot_lut,
+                            int lut_size, int64_t ts_lo, int64_t ts_hi,
+                            int32_t& slot, bool null_lut_is_all = false) {
+  slot = 0;
+  if (t < ts_lo || t >= ts_hi) return false;
+  if (null_lut_is_all && slot_lut == nullptr) return true;
+  const int32_t s = series[i];
+  if (s < 0 || s >= lut_size) return false;
+  slot = slot_lut[s];
+  return slot >= 0;
 }
 
+// ------------------------------------------------------------- K5 finish
 // decode min/max key arrays into f64 (count==0 → NaN)
 __global__ void decode_minmax_kernel(
     const unsigned long long* __restrict__ minkey,
@@ -105,8 +97,8 @@ __global__ void decode_minmax_kernel(
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     if (cnt[i] == 0) {
-      out_min[i] = __longlong_as_double(0x7FF8000000000000LL);  // NaN
-      out_max[i] = __longlong_as_double(0x7FF8000000000000LL);
+      out_min[i] = quiet_nan();
+      out_max[i] = quiet_nan();
     } else {
       out_min[i] = key_to_f64(minkey[i]);
       out_max[i] = key_to_f64(maxkey[i]);
@@ -123,13 +115,9 @@ __global__ void filter_series_time_kernel(
     bool* __restrict__ keep) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const int64_t t = ts[i];
-    bool k = (t >= ts_lo) & (t < ts_hi);
-    if (k && slot_lut != nullptr) {
-      const int32_t s = series[i];
-      k = (s >= 0) & (s < lut_size) && (slot_lut[s] >= 0);
-    }
-    keep[i] = k;
+    int32_t slot;
+    keep[i] = visible_row(ts[i], series, i, slot_lut, lut_size, ts_lo, ts_hi,
+                          slot, /*null_lut_is_all=*/true);
   }
 }
 
@@ -224,125 +212,19 @@ __global__ void __launch_bounds__(256) merge_last_non_null_kernel(
   }
 }
 
-// ------------------------------------------------- K5 two-phase (sorted-aware)
-//
-// The naive per-row atomic version above costs nf*4+1 atomics PER ROW —
-// rocprof showed it running at ~1.4% of HBM bandwidth on the TSBS
-// double-groupby shape (4.2B atomic RMWs over 104M rows). Scan sources are
-// (series, ts)-sorted, so consecutive rows usually land in the SAME
-// (slot, bucket) cell: phase A computes the cell id per row once (reused by
-// every field); phase B gives each thread a contiguous row chunk per field
-// and accumulates in REGISTERS, flushing atomics only when the cell changes
-// (≈ once per run instead of once per row). Correct for unsorted input too
-// (degenerates to per-row flushes).
-
-__global__ void bucket_cell_kernel(
-    const int64_t* __restrict__ ts,
-    const int32_t* __restrict__ series,
-    const int32_t* __restrict__ slot_lut, int lut_size,
-    int64_t ts_lo, int64_t ts_hi, int64_t origin, int64_t bucket_ms,
-    int n_buckets, int64_t n,
-    int32_t* __restrict__ cell,                 // [n] slot*n_buckets+b or -1
-    unsigned long long* __restrict__ out_rows,  // [n_slots*n_buckets]
-    int rows_chunk) {
-  // rows-count accumulation with chunked run detection
-  const int64_t nchunks = (n + rows_chunk - 1) / rows_chunk;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < nchunks; c += stride) {
-    const int64_t lo = c * rows_chunk;
-    const int64_t hi = min(lo + rows_chunk, n);
-    int32_t cur = -1;
-    unsigned long long run = 0;
-    for (int64_t i = lo; i < hi; i++) {
-      const int64_t t = ts[i];
-      const int32_t s = series[i];
-      int32_t cl = -1;
-      if (t >= ts_lo && t < ts_hi && s >= 0 && s < lut_size) {
-        const int32_t slot = slot_lut[s];
-        if (slot >= 0) {
-          const int64_t b = bucket_index(t, origin, bucket_ms);
-          if (b >= 0 && b < n_buckets) cl = slot * n_buckets + (int32_t)b;
-        }
-      }
-      cell[i] = cl;
-      if (cl == cur) {
-        run++;
-      } else {
-        if (cur >= 0 && run) atomicAdd(&out_rows[cur], run);
-        cur = cl;
-        run = 1;
-      }
-    }
-    if (cur >= 0 && run) atomicAdd(&out_rows[cur], run);
-  }
-}
-
-__global__ void field_bucket_agg_kernel(
-    const int32_t* __restrict__ cell,
-    const double* __restrict__ fields, int64_t field_stride,
-    const int32_t* __restrict__ field_idx, int nf,
-    int64_t n, int64_t cells_per_field, int rows_chunk,
-    double* __restrict__ out_sum,
-    unsigned long long* __restrict__ out_cnt,
-    unsigned long long* __restrict__ out_min,
-    unsigned long long* __restrict__ out_max) {
-  const int64_t nchunks = (n + rows_chunk - 1) / rows_chunk;
-  const int64_t total = nchunks * nf;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
-    // consecutive threads take consecutive chunks of the SAME field
-    const int f = (int)(t / nchunks);
-    const int64_t c = t % nchunks;
-    const double* __restrict__ col = fields + (int64_t)field_idx[f] * field_stride;
-    double* __restrict__ o_sum = out_sum + (int64_t)f * cells_per_field;
-    unsigned long long* __restrict__ o_cnt = out_cnt + (int64_t)f * cells_per_field;
-    unsigned long long* __restrict__ o_min = out_min + (int64_t)f * cells_per_field;
-    unsigned long long* __restrict__ o_max = out_max + (int64_t)f * cells_per_field;
-    const int64_t lo = c * rows_chunk;
-    const int64_t hi = min(lo + rows_chunk, n);
-    int32_t cur = -1;
-    double a_sum = 0.0;
-    unsigned long long a_cnt = 0;
-    uint64_t a_min = ~0ULL, a_max = 0ULL;
-    for (int64_t i = lo; i < hi; i++) {
-      const int32_t cl = cell[i];
-      if (cl != cur) {
-        if (cur >= 0 && a_cnt) {
-          atomicAdd(&o_sum[cur], a_sum);
-          atomicAdd(&o_cnt[cur], a_cnt);
-          atomicMin(&o_min[cur], a_min);
-          atomicMax(&o_max[cur], a_max);
-        }
-        cur = cl; a_sum = 0.0; a_cnt = 0; a_min = ~0ULL; a_max = 0ULL;
-      }
-      if (cl < 0) continue;
-      const double v = col[i];
-      if (isnan(v)) continue;
-      a_sum += v;
-      a_cnt++;
-      const uint64_t k = f64_to_key(v);
-      a_min = min(a_min, (uint64_t)k);
-      a_max = max(a_max, (uint64_t)k);
-    }
-    if (cur >= 0 && a_cnt) {
-      atomicAdd(&o_sum[cur], a_sum);
-      atomicAdd(&o_cnt[cur], a_cnt);
-      atomicMin(&o_min[cur], a_min);
-      atomicMax(&o_max[cur], a_max);
-    }
-  }
-}
-
-// ---------------------------------------------- K5 v3: LDS-privatized tiles
-//
-// PMC (FETCH_SIZE) showed the chunked-run kernels fetching 8-10x the input
-// bytes: per-thread contiguous chunks make every wavefront touch 64 cache
-// lines per step (uncoalesced). v3 restores coalescing — threads stride the
-// tile contiguously — and privatizes the accumulator table in LDS: a tile
-// of sorted rows spans only a few (slot,bucket) cells, so per-element LDS
-// atomics replace global ones, flushed once per tile. Tiles whose cell
-// range exceeds the LDS table fall back to global atomics (still with
-// coalesced loads).
+// ---------------------------------------------------------------- K1+K2+K5
+// Fused filter + time-bucket aggregate in two launches.
+// bucket_cell_coalesced_kernel: one thread per row, coalesced, writes the
+// row's (slot, bucket) cell id, slot * n_buckets + bucket, or -1 where the
+// row is filtered out; every field reuses it.
+// field_bucket_agg_lds_kernel: one block per tile of AGG_TILE rows, threads
+// striding the tile contiguously so loads stay coalesced. Scan sources are
+// (series, ts)-sorted, so a tile spans few cells: the accumulator table of
+// the tile's cell range is privatized in LDS (per-element LDS atomics) and
+// flushed to the global [nf, n_slots, n_buckets] accumulators once per tile
+// and field. A tile whose cell range exceeds LDS_CELLS (unsorted input)
+// falls back to global atomics, still with coalesced loads.
+// fields: column-major per field: fields[f * field_stride + row]
 
 __global__ void bucket_cell_coalesced_kernel(
     const int64_t* __restrict__ ts,
@@ -354,21 +236,14 @@ __global__ void bucket_cell_coalesced_kernel(
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     const int64_t t = ts[i];
-    const int32_t sId = series[i];
-    int32_t cl = -1;
-    if (t >= ts_lo && t < ts_hi && sId >= 0 && sId < lut_size) {
-      const int32_t slot = slot_lut[sId];
-      if (slot >= 0) {
-        const int64_t b = bucket_index(t, origin, bucket_ms);
-        if (b >= 0 && b < n_buckets) cl = slot * n_buckets + (int32_t)b;
-      }
+    int32_t slot, cl = -1;
+    if (visible_row(t, series, i, slot_lut, lut_size, ts_lo, ts_hi, slot)) {
+      const int64_t b = bucket_index(t, origin, bucket_ms);
+      if (b >= 0 && b < n_buckets) cl = slot * n_buckets + (int32_t)b;
     }
     cell[i] = cl;
   }
 }
-
-#define AGG_TILE 8192
-#define LDS_CELLS 1024
 
 __global__ void field_bucket_agg_lds_kernel(
     const int32_t* __restrict__ cell,
@@ -492,11 +367,8 @@ __global__ void series_last_ts_kernel(
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     const int64_t t = ts[i];
-    if (t < ts_lo || t >= ts_hi) continue;
-    const int32_t s = series[i];
-    if (s < 0 || s >= lut_size) continue;
-    const int32_t slot = slot_lut[s];
-    if (slot < 0) continue;
+    int32_t slot;
+    if (!visible_row(t, series, i, slot_lut, lut_size, ts_lo, ts_hi, slot)) continue;
     atomicMax(&best_key[slot], (unsigned long long)i64_to_key(t));
   }
 }
@@ -514,11 +386,8 @@ __global__ void series_last_row_kernel(
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     const int64_t t = ts[i];
-    if (t < ts_lo || t >= ts_hi) continue;
-    const int32_t s = series[i];
-    if (s < 0 || s >= lut_size) continue;
-    const int32_t slot = slot_lut[s];
-    if (slot < 0) continue;
+    int32_t slot;
+    if (!visible_row(t, series, i, slot_lut, lut_size, ts_lo, ts_hi, slot)) continue;
     if ((unsigned long long)i64_to_key(t) != best_key[slot]) continue;
     // +1 so "no row" (0) is distinguishable from src 0 row 0
     atomicMax(&best_row[slot], (src_tag << 40) | ((unsigned long long)i + 1));
@@ -541,20 +410,6 @@ enum PromMode {
   PM_RESETS = 14, PM_CHANGES = 15, PM_STDDEV = 16, PM_STDVAR = 17,
   PM_ABSENT_OT = 18, PM_QUANTILE_OT = 19, PM_LAST_TS = 20,
 };
-
-DEV_INLINE double prom_nan() { return __longlong_as_double(0x7FF8000000000000LL); }
-
-// IEEE-754 double ↔ totally-ordered u64 (sign-flip transform): key order ==
-// numeric order, so order statistics can be selected bitwise.
-DEV_INLINE uint64_t f64_sort_key(double v) {
-  const uint64_t u = (uint64_t)__double_as_longlong(v);
-  return (u & 0x8000000000000000ULL) ? ~u : (u | 0x8000000000000000ULL);
-}
-DEV_INLINE double sort_key_f64(uint64_t k) {
-  const uint64_t u = (k & 0x8000000000000000ULL)
-      ? (k ^ 0x8000000000000000ULL) : ~k;
-  return __longlong_as_double((long long)u);
-}
 
 __global__ void prom_range_eval_kernel(
     const int64_t* __restrict__ ts,
@@ -581,7 +436,7 @@ __global__ void prom_range_eval_kernel(
     while (a < b) { int64_t m = (a + b) >> 1; if (ts[m] <= te) a = m + 1; else b = m; }
     const int64_t w_hi = a;                                     // exclusive
     const int64_t cnt = w_hi - w_lo;
-    double r = prom_nan();
+    double r = quiet_nan();
     if (mode == PM_INSTANT) {
       if (cnt > 0) r = vals[w_hi - 1];
     } else if (mode == PM_LAST) {
@@ -593,7 +448,7 @@ __global__ void prom_range_eval_kernel(
     } else if (mode == PM_COUNT) {
       if (cnt > 0) r = (double)cnt;
     } else if (mode == PM_ABSENT_OT) {
-      r = (cnt > 0) ? prom_nan() : 1.0;
+      r = (cnt > 0) ? quiet_nan() : 1.0;
     } else if (cnt > 0 && (mode == PM_SUM || mode == PM_AVG || mode == PM_MIN ||
                            mode == PM_MAX || mode == PM_STDDEV || mode == PM_STDVAR)) {
       double sum = 0, mn = vals[w_lo], mx = vals[w_lo];
@@ -653,7 +508,7 @@ __global__ void prom_range_eval_kernel(
       } else {
         double v2 = vals[w_hi - 1], v1 = vals[w_hi - 2];
         double d = (v2 < v1) ? v2 : dv;   // reset → use raw value
-        r = (dt > 0) ? d / dt : prom_nan();
+        r = (dt > 0) ? d / dt : quiet_nan();
       }
     } else if (cnt >= 2 && (mode == PM_DERIV || mode == PM_PREDICT)) {
       // least-squares slope/intercept, x relative to window end (Prometheus
@@ -721,7 +576,7 @@ __global__ void prom_range_eval_kernel(
             const uint64_t b = 1ULL << bit;
             int64_t cnt0 = 0;
             for (int64_t j = w_lo; j < w_hi; j++) {
-              const uint64_t kj = f64_sort_key(vals[j]);
+              const uint64_t kj = f64_to_key(vals[j]);
               cnt0 += ((kj & high_mask) == prefix) & !(kj & b);
             }
             if (k >= cnt0) { k -= cnt0; prefix |= b; }
@@ -731,13 +586,13 @@ __global__ void prom_range_eval_kernel(
           uint64_t next = ~0ULL;
           bool has_next = false;
           for (int64_t j = w_lo; j < w_hi; j++) {
-            const uint64_t kj = f64_sort_key(vals[j]);
+            const uint64_t kj = f64_to_key(vals[j]);
             if (kj < kk) less++;
             else if (kj == kk) eq++;
             else if (kj < next) { next = kj; has_next = true; }
           }
-          vk1 = sort_key_f64(kk);
-          vk2 = (k2 < less + eq || !has_next) ? vk1 : sort_key_f64(next);
+          vk1 = key_to_f64(kk);
+          vk2 = (k2 < less + eq || !has_next) ? vk1 : key_to_f64(next);
         }
         r = vk1 + (vk2 - vk1) * (rank - (double)k1);
       }
@@ -768,12 +623,6 @@ __global__ void prom_range_eval_kernel(
 // lds_cap (0..16) lowers that span at run time, 0 = global atomics only,
 // which is how the two paths are timed against each other.
 // Cell ids outside [0, n_cells) are skipped like -1.
-
-#define QSEL_TILE 2048
-#define QSEL_BLOCK 256
-#define QSEL_ROWS (QSEL_TILE / QSEL_BLOCK)
-#define QSEL_LDS_CELLS 16
-#define QSEL_MAX_GRID 1024
 
 // Loads the tile's cell ids into registers (-1 for rows past n or ids out of
 // range) and reduces their span through s_lo/s_hi. Returns false when no row
@@ -846,7 +695,7 @@ __global__ void __launch_bounds__(QSEL_BLOCK) quantile_hist_kernel(
           if (c[j] < 0) continue;
           const double v = col[t0 + (int64_t)j * QSEL_BLOCK + tid];
           if (isnan(v)) continue;
-          const uint64_t key = f64_sort_key(v);
+          const uint64_t key = f64_to_key(v);
           const int lc = c[j] - lo;
           if (pass > 0 && (key >> hi_shift) != (s_prefix[lc] >> hi_shift)) continue;
           atomicAdd(&s_hist[lc * 256 + (int)((key >> byte_shift) & 0xFF)], 1u);
@@ -863,7 +712,7 @@ __global__ void __launch_bounds__(QSEL_BLOCK) quantile_hist_kernel(
           if (c[j] < 0) continue;
           const double v = col[t0 + (int64_t)j * QSEL_BLOCK + tid];
           if (isnan(v)) continue;
-          const uint64_t key = f64_sort_key(v);
+          const uint64_t key = f64_to_key(v);
           const int64_t sc = sbase + c[j];
           if (pass > 0 && (key >> hi_shift) != (prefix[sc] >> hi_shift)) continue;
           atomicAdd(&hist[sc * 256 + (int)((key >> byte_shift) & 0xFF)], 1u);
@@ -965,7 +814,7 @@ __global__ void __launch_bounds__(QSEL_BLOCK) quantile_next_kernel(
           if (c[j] < 0) continue;
           const double v = col[t0 + (int64_t)j * QSEL_BLOCK + tid];
           if (isnan(v)) continue;
-          const uint64_t key = f64_sort_key(v);
+          const uint64_t key = f64_to_key(v);
           const int lc = c[j] - lo;
           if (key <= s_prefix[lc]) atomicAdd(&s_le[lc], 1u);
           else atomicMin(&s_next[lc], (unsigned long long)key);
@@ -982,7 +831,7 @@ __global__ void __launch_bounds__(QSEL_BLOCK) quantile_next_kernel(
           if (c[j] < 0) continue;
           const double v = col[t0 + (int64_t)j * QSEL_BLOCK + tid];
           if (isnan(v)) continue;
-          const uint64_t key = f64_sort_key(v);
+          const uint64_t key = f64_to_key(v);
           const int64_t sc = sbase + c[j];
           if (key <= prefix[sc]) atomicAdd(&le[sc], 1ULL);
           else atomicMin(&next[sc], (unsigned long long)key);
@@ -1002,14 +851,14 @@ __global__ void quantile_finish_kernel(
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < QC; i += stride) {
     if (cnt[i] == 0) {
-      out_lo[i] = prom_nan();
-      out_hi[i] = prom_nan();
+      out_lo[i] = quiet_nan();
+      out_hi[i] = quiet_nan();
       continue;
     }
-    const double lo = sort_key_f64(prefix[i]);
+    const double lo = key_to_f64(prefix[i]);
     const bool same = (k1[i] + 1 < (int64_t)le[i]) || next[i] == ~0ULL;
     out_lo[i] = lo;
-    out_hi[i] = same ? lo : sort_key_f64(next[i]);
+    out_hi[i] = same ? lo : key_to_f64(next[i]);
   }
 }
 
@@ -1081,203 +930,6 @@ __global__ void scatter_append_packed_kernel(
     }
   }
 }
-
-// ---------------------------------------------------------------- launchers
-
-static inline int grid_for(int64_t n, int block) {
-  int64_t g = (n + block - 1) / block;
-  if (g > 2048) g = 2048;  // G11: cap + grid-stride
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
-void launch_ts_bucket_agg(
-    const int64_t* ts, const int32_t* series, const double* fields,
-    int64_t field_stride, const int32_t* field_idx, int nf,
-    const int32_t* slot_lut, int lut_size,
-    int64_t ts_lo, int64_t ts_hi, int64_t origin, int64_t bucket_ms,
-    int n_slots, int n_buckets, int64_t n,
-    double* out_sum, unsigned long long* out_cnt,
-    unsigned long long* out_min, unsigned long long* out_max,
-    unsigned long long* out_rows,
-    hipStream_t stream) {
-  hipLaunchKernelGGL(ts_bucket_agg_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream,
-      ts, series, fields, field_stride, field_idx, nf, slot_lut, lut_size,
-      ts_lo, ts_hi, origin, bucket_ms, n_slots, n_buckets, n,
-      out_sum, out_cnt, out_min, out_max, out_rows);
-}
-
-void launch_decode_minmax(
-    const unsigned long long* minkey, const unsigned long long* maxkey,
-    const unsigned long long* cnt, double* out_min, double* out_max,
-    int64_t n, hipStream_t stream) {
-  hipLaunchKernelGGL(decode_minmax_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream,
-      minkey, maxkey, cnt, out_min, out_max, n);
-}
-
-void launch_filter_series_time(
-    const int64_t* ts, const int32_t* series, const int32_t* slot_lut,
-    int lut_size, int64_t ts_lo, int64_t ts_hi, int64_t n, bool* keep,
-    hipStream_t stream) {
-  hipLaunchKernelGGL(filter_series_time_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream,
-      ts, series, slot_lut, lut_size, ts_lo, ts_hi, n, keep);
-}
-
-void launch_dedup_mark_last(
-    const int32_t* series, const int64_t* ts, int64_t n, bool* keep,
-    hipStream_t stream) {
-  hipLaunchKernelGGL(dedup_mark_last_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream,
-      series, ts, n, keep);
-}
-
-void launch_merge_last_non_null(
-    const int64_t* kidx, int64_t g, const double* fields, int64_t field_stride,
-    int nf, double* out, hipStream_t stream) {
-  hipLaunchKernelGGL(merge_last_non_null_kernel, dim3(grid_for(g, 256)), dim3(256), 0, stream,
-      kidx, g, fields, field_stride, nf, out);
-}
-
-void launch_bucket_agg2(
-    const int64_t* ts, const int32_t* series, const double* fields,
-    int64_t field_stride, const int32_t* field_idx, int nf,
-    const int32_t* slot_lut, int lut_size,
-    int64_t ts_lo, int64_t ts_hi, int64_t origin, int64_t bucket_ms,
-    int n_slots, int n_buckets, int64_t n,
-    int32_t* cell_buf,
-    double* out_sum, unsigned long long* out_cnt,
-    unsigned long long* out_min, unsigned long long* out_max,
-    unsigned long long* out_rows, hipStream_t stream) {
-  // v3 (PMC-guided): coalesced cell pass + LDS-privatized tile aggregation
-  hipLaunchKernelGGL(bucket_cell_coalesced_kernel,
-      dim3(grid_for(n, 256)), dim3(256), 0, stream,
-      ts, series, slot_lut, lut_size, ts_lo, ts_hi, origin, bucket_ms,
-      n_buckets, n, cell_buf);
-  {
-    // Tiles beyond the grid are taken by the kernel's tile grid-stride loop
-    // (only past 8192 tiles = 67M rows, too large for the test suite).
-    // n == 0 would give a zero-sized grid, which HIP rejects: clamp to 1.
-    const int64_t ntiles = (n + AGG_TILE - 1) / AGG_TILE;
-    const int grid = (int)max(min(ntiles, (int64_t)8192), (int64_t)1);
-    hipLaunchKernelGGL(field_bucket_agg_lds_kernel,
-        dim3(grid), dim3(256), 0, stream,
-        cell_buf, fields, field_stride, field_idx, nf, n,
-        (int64_t)n_slots * n_buckets,
-        out_sum, out_cnt, out_min, out_max, out_rows);
-  }
-}
-
-void launch_scatter_append(
-    const int64_t* ts, const int32_t* series, const double* fields,
-    const int32_t* region_of, const int64_t* dst_off,
-    int64_t* const* ts_ptrs, int32_t* const* se_ptrs, double* const* f_ptrs,
-    const int64_t* strides, int nf, int64_t n, hipStream_t stream) {
-  hipLaunchKernelGGL(scatter_append_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream,
-      ts, series, fields, region_of, dst_off, ts_ptrs, se_ptrs, f_ptrs,
-      strides, nf, n);
-}
-
-void launch_scatter_append_packed(
-    const unsigned char* stage, int64_t n, int nf, const PackedRegions& regs,
-    hipStream_t stream) {
-  hipLaunchKernelGGL(scatter_append_packed_kernel,
-      dim3(grid_for(n * (int64_t)(nf + 1), 256)), dim3(256), 0, stream,
-      stage, n, nf, regs);
-}
-
-void launch_series_last(
-    const int64_t* ts, const int32_t* series, const int32_t* slot_lut,
-    int lut_size, int64_t ts_lo, int64_t ts_hi, int64_t n,
-    unsigned long long* best_key, hipStream_t stream) {
-  hipLaunchKernelGGL(series_last_ts_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream,
-      ts, series, slot_lut, lut_size, ts_lo, ts_hi, n, best_key);
-}
-
-void launch_prom_range_eval(
-    const int64_t* ts, const double* vals, const int64_t* seg_lo,
-    const int64_t* seg_hi, int S, int T, int64_t t0, int64_t step_ms,
-    int64_t range_ms, int64_t offset_ms, double param, int mode, double* out,
-    hipStream_t stream) {
-  const int64_t total = (int64_t)S * T;
-  hipLaunchKernelGGL(prom_range_eval_kernel, dim3(grid_for(total, 256)), dim3(256), 0, stream,
-      ts, vals, seg_lo, seg_hi, S, T, t0, step_ms, range_ms, offset_ms,
-      param, mode, out);
-}
-
-void launch_series_last_row(
-    const int64_t* ts, const int32_t* series, const int32_t* slot_lut,
-    int lut_size, int64_t ts_lo, int64_t ts_hi, int64_t n,
-    const unsigned long long* best_key, unsigned long long src_tag,
-    unsigned long long* best_row, hipStream_t stream) {
-  hipLaunchKernelGGL(series_last_row_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream,
-      ts, series, slot_lut, lut_size, ts_lo, ts_hi, n, best_key, src_tag, best_row);
-}
-
-// phase A of K5 on its own: (slot, bucket) cell id per row, -1 = filtered out
-void launch_bucket_cells(
-    const int64_t* ts, const int32_t* series, const int32_t* slot_lut,
-    int lut_size, int64_t ts_lo, int64_t ts_hi, int64_t origin,
-    int64_t bucket_ms, int n_buckets, int64_t n, int32_t* cell,
-    hipStream_t stream) {
-  hipLaunchKernelGGL(bucket_cell_coalesced_kernel,
-      dim3(grid_for(n, 256)), dim3(256), 0, stream,
-      ts, series, slot_lut, lut_size, ts_lo, ts_hi, origin, bucket_ms,
-      n_buckets, n, cell);
-}
-
-static inline int qsel_grid(int64_t n) {
-  const int64_t ntiles = (n + QSEL_TILE - 1) / QSEL_TILE;
-  return (int)max(min(ntiles, (int64_t)QSEL_MAX_GRID), (int64_t)1);
-}
-
-void launch_quantile_hist(
-    const int32_t* cell, const double* fields, int64_t field_stride,
-    const int32_t* field_idx, int n_field_rows, const int32_t* field_of_sel,
-    int Q, int64_t n, int n_cells, int pass, int lds_cap,
-    const unsigned long long* prefix, unsigned int* hist, hipStream_t stream) {
-  lds_cap = min(lds_cap, QSEL_LDS_CELLS);
-  hipLaunchKernelGGL(quantile_hist_kernel, dim3(qsel_grid(n)), dim3(QSEL_BLOCK),
-      0, stream, cell, fields, field_stride, field_idx, n_field_rows,
-      field_of_sel, Q, n, n_cells, pass, lds_cap, prefix, hist);
-}
-
-void launch_quantile_pick(
-    unsigned int* hist, const double* p_of_sel, int n_cells, int64_t QC,
-    int pass, unsigned long long* prefix, int64_t* k_left, int64_t* k1,
-    int64_t* cnt, hipStream_t stream) {
-  const int64_t blocks = (QC + 3) / 4;           // 4 wavefronts per block
-  const int grid = (int)max(min(blocks, (int64_t)65536), (int64_t)1);
-  hipLaunchKernelGGL(quantile_pick_kernel, dim3(grid), dim3(QSEL_BLOCK), 0,
-      stream, hist, p_of_sel, n_cells, QC, pass, prefix, k_left, k1, cnt);
-}
-
-void launch_quantile_next(
-    const int32_t* cell, const double* fields, int64_t field_stride,
-    const int32_t* field_idx, int n_field_rows, const int32_t* field_of_sel,
-    int Q, int64_t n, int n_cells, int lds_cap, const unsigned long long* prefix,
-    unsigned long long* le, unsigned long long* next, hipStream_t stream) {
-  lds_cap = min(lds_cap, QSEL_LDS_CELLS);
-  hipLaunchKernelGGL(quantile_next_kernel, dim3(qsel_grid(n)), dim3(QSEL_BLOCK),
-      0, stream, cell, fields, field_stride, field_idx, n_field_rows,
-      field_of_sel, Q, n, n_cells, lds_cap, prefix, le, next);
-}
-
-void launch_quantile_finish(
-    const unsigned long long* prefix, const int64_t* k1, const int64_t* cnt,
-    const unsigned long long* le, const unsigned long long* next, int64_t QC,
-    double* out_lo, double* out_hi, hipStream_t stream) {
-  hipLaunchKernelGGL(quantile_finish_kernel, dim3(grid_for(QC, 256)), dim3(256),
-      0, stream, prefix, k1, cnt, le, next, QC, out_lo, out_hi);
-}
-
-// launch geometry of the selection kernels, for tests that size their inputs
-// to reach every path: {tile rows, LDS cell capacity, grid cap}
-void quantile_launch_config(int64_t out[3]) {
-  out[0] = QSEL_TILE;
-  out[1] = QSEL_LDS_CELLS;
-  out[2] = QSEL_MAX_GRID;
-}
-
-
 
 // ------------------------------------------------- K11 RLE/bit-packed expand
 // Parquet hybrid RLE/bit-packed dictionary indices → i32, fully parallel:
@@ -1424,7 +1076,6 @@ __global__ void gorilla_decode_kernel(
 //                           64-bit output word from LDS and stores it whole.
 // The exclusive scan of the sizes between the last two runs in the binding.
 constexpr int GENC_THREADS = 256;
-constexpr int GENC_MAX_BLOCK = 4096;        // values per codec block (LDS stage)
 constexpr unsigned GENC_NONFINITE = 1u << 5;
 constexpr unsigned GENC_ALL_SCALES = 0x1Fu;
 
@@ -1613,14 +1264,183 @@ __global__ void __launch_bounds__(GENC_THREADS) gorilla_write_kernel(
   }
 }
 
-void launch_rle_expand_indices(
+// ---------------------------------------------------------------- launchers
+// Defined by qualified name: a definition that matches no declaration of
+// kernels.h is a compile error, not a new overload.
+
+static inline int grid_for(int64_t n, int block) {
+  int64_t g = (n + block - 1) / block;
+  if (g > 2048) g = 2048;  // G11: cap + grid-stride
+  if (g < 1) g = 1;
+  return (int)g;
+}
+
+static inline int qsel_grid(int64_t n) {
+  const int64_t ntiles = (n + QSEL_TILE - 1) / QSEL_TILE;
+  return (int)max(min(ntiles, (int64_t)QSEL_MAX_GRID), (int64_t)1);
+}
+
+}  // namespace gdb_hip
+
+void gdb_hip::launch_decode_minmax(
+    const unsigned long long* minkey, const unsigned long long* maxkey,
+    const unsigned long long* cnt, double* out_min, double* out_max,
+    int64_t n, hipStream_t stream) {
+  hipLaunchKernelGGL(decode_minmax_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream,
+      minkey, maxkey, cnt, out_min, out_max, n);
+}
+
+void gdb_hip::launch_filter_series_time(
+    const int64_t* ts, const int32_t* series, const int32_t* slot_lut,
+    int lut_size, int64_t ts_lo, int64_t ts_hi, int64_t n, bool* keep,
+    hipStream_t stream) {
+  hipLaunchKernelGGL(filter_series_time_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream,
+      ts, series, slot_lut, lut_size, ts_lo, ts_hi, n, keep);
+}
+
+void gdb_hip::launch_dedup_mark_last(
+    const int32_t* series, const int64_t* ts, int64_t n, bool* keep,
+    hipStream_t stream) {
+  hipLaunchKernelGGL(dedup_mark_last_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream,
+      series, ts, n, keep);
+}
+
+void gdb_hip::launch_merge_last_non_null(
+    const int64_t* kidx, int64_t g, const double* fields, int64_t field_stride,
+    int nf, double* out, hipStream_t stream) {
+  hipLaunchKernelGGL(merge_last_non_null_kernel, dim3(grid_for(g, 256)), dim3(256), 0, stream,
+      kidx, g, fields, field_stride, nf, out);
+}
+
+void gdb_hip::launch_ts_bucket_agg(
+    const int64_t* ts, const int32_t* series, const double* fields,
+    int64_t field_stride, const int32_t* field_idx, int nf,
+    const int32_t* slot_lut, int lut_size,
+    int64_t ts_lo, int64_t ts_hi, int64_t origin, int64_t bucket_ms,
+    int n_slots, int n_buckets, int64_t n,
+    int32_t* cell_buf,
+    double* out_sum, unsigned long long* out_cnt,
+    unsigned long long* out_min, unsigned long long* out_max,
+    unsigned long long* out_rows, hipStream_t stream) {
+  launch_bucket_cells(ts, series, slot_lut, lut_size, ts_lo, ts_hi, origin,
+                      bucket_ms, n_buckets, n, cell_buf, stream);
+  // Tiles beyond the grid are taken by the kernel's tile grid-stride loop
+  // (only past 8192 tiles = 67M rows, too large for the test suite).
+  // n == 0 would give a zero-sized grid, which HIP rejects: clamp to 1.
+  const int64_t ntiles = (n + AGG_TILE - 1) / AGG_TILE;
+  const int grid = (int)max(min(ntiles, (int64_t)8192), (int64_t)1);
+  hipLaunchKernelGGL(field_bucket_agg_lds_kernel,
+      dim3(grid), dim3(256), 0, stream,
+      cell_buf, fields, field_stride, field_idx, nf, n,
+      (int64_t)n_slots * n_buckets,
+      out_sum, out_cnt, out_min, out_max, out_rows);
+}
+
+void gdb_hip::launch_scatter_append(
+    const int64_t* ts, const int32_t* series, const double* fields,
+    const int32_t* region_of, const int64_t* dst_off,
+    int64_t* const* ts_ptrs, int32_t* const* se_ptrs, double* const* f_ptrs,
+    const int64_t* strides, int nf, int64_t n, hipStream_t stream) {
+  hipLaunchKernelGGL(scatter_append_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream,
+      ts, series, fields, region_of, dst_off, ts_ptrs, se_ptrs, f_ptrs,
+      strides, nf, n);
+}
+
+void gdb_hip::launch_scatter_append_packed(
+    const unsigned char* stage, int64_t n, int nf, const PackedRegions& regs,
+    hipStream_t stream) {
+  hipLaunchKernelGGL(scatter_append_packed_kernel,
+      dim3(grid_for(n * (int64_t)(nf + 1), 256)), dim3(256), 0, stream,
+      stage, n, nf, regs);
+}
+
+void gdb_hip::launch_series_last(
+    const int64_t* ts, const int32_t* series, const int32_t* slot_lut,
+    int lut_size, int64_t ts_lo, int64_t ts_hi, int64_t n,
+    unsigned long long* best_key, hipStream_t stream) {
+  hipLaunchKernelGGL(series_last_ts_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream,
+      ts, series, slot_lut, lut_size, ts_lo, ts_hi, n, best_key);
+}
+
+void gdb_hip::launch_prom_range_eval(
+    const int64_t* ts, const double* vals, const int64_t* seg_lo,
+    const int64_t* seg_hi, int S, int T, int64_t t0, int64_t step_ms,
+    int64_t range_ms, int64_t offset_ms, double param, int mode, double* out,
+    hipStream_t stream) {
+  const int64_t total = (int64_t)S * T;
+  hipLaunchKernelGGL(prom_range_eval_kernel, dim3(grid_for(total, 256)), dim3(256), 0, stream,
+      ts, vals, seg_lo, seg_hi, S, T, t0, step_ms, range_ms, offset_ms,
+      param, mode, out);
+}
+
+void gdb_hip::launch_series_last_row(
+    const int64_t* ts, const int32_t* series, const int32_t* slot_lut,
+    int lut_size, int64_t ts_lo, int64_t ts_hi, int64_t n,
+    const unsigned long long* best_key, unsigned long long src_tag,
+    unsigned long long* best_row, hipStream_t stream) {
+  hipLaunchKernelGGL(series_last_row_kernel, dim3(grid_for(n, 256)), dim3(256), 0, stream,
+      ts, series, slot_lut, lut_size, ts_lo, ts_hi, n, best_key, src_tag, best_row);
+}
+
+void gdb_hip::launch_bucket_cells(
+    const int64_t* ts, const int32_t* series, const int32_t* slot_lut,
+    int lut_size, int64_t ts_lo, int64_t ts_hi, int64_t origin,
+    int64_t bucket_ms, int n_buckets, int64_t n, int32_t* cell,
+    hipStream_t stream) {
+  hipLaunchKernelGGL(bucket_cell_coalesced_kernel,
+      dim3(grid_for(n, 256)), dim3(256), 0, stream,
+      ts, series, slot_lut, lut_size, ts_lo, ts_hi, origin, bucket_ms,
+      n_buckets, n, cell);
+}
+
+void gdb_hip::launch_quantile_hist(
+    const int32_t* cell, const double* fields, int64_t field_stride,
+    const int32_t* field_idx, int n_field_rows, const int32_t* field_of_sel,
+    int Q, int64_t n, int n_cells, int pass, int lds_cap,
+    const unsigned long long* prefix, unsigned int* hist, hipStream_t stream) {
+  lds_cap = min(lds_cap, QSEL_LDS_CELLS);
+  hipLaunchKernelGGL(quantile_hist_kernel, dim3(qsel_grid(n)), dim3(QSEL_BLOCK),
+      0, stream, cell, fields, field_stride, field_idx, n_field_rows,
+      field_of_sel, Q, n, n_cells, pass, lds_cap, prefix, hist);
+}
+
+void gdb_hip::launch_quantile_pick(
+    unsigned int* hist, const double* p_of_sel, int n_cells, int64_t QC,
+    int pass, unsigned long long* prefix, int64_t* k_left, int64_t* k1,
+    int64_t* cnt, hipStream_t stream) {
+  const int64_t blocks = (QC + 3) / 4;           // 4 wavefronts per block
+  const int grid = (int)max(min(blocks, (int64_t)65536), (int64_t)1);
+  hipLaunchKernelGGL(quantile_pick_kernel, dim3(grid), dim3(QSEL_BLOCK), 0,
+      stream, hist, p_of_sel, n_cells, QC, pass, prefix, k_left, k1, cnt);
+}
+
+void gdb_hip::launch_quantile_next(
+    const int32_t* cell, const double* fields, int64_t field_stride,
+    const int32_t* field_idx, int n_field_rows, const int32_t* field_of_sel,
+    int Q, int64_t n, int n_cells, int lds_cap, const unsigned long long* prefix,
+    unsigned long long* le, unsigned long long* next, hipStream_t stream) {
+  lds_cap = min(lds_cap, QSEL_LDS_CELLS);
+  hipLaunchKernelGGL(quantile_next_kernel, dim3(qsel_grid(n)), dim3(QSEL_BLOCK),
+      0, stream, cell, fields, field_stride, field_idx, n_field_rows,
+      field_of_sel, Q, n, n_cells, lds_cap, prefix, le, next);
+}
+
+void gdb_hip::launch_quantile_finish(
+    const unsigned long long* prefix, const int64_t* k1, const int64_t* cnt,
+    const unsigned long long* le, const unsigned long long* next, int64_t QC,
+    double* out_lo, double* out_hi, hipStream_t stream) {
+  hipLaunchKernelGGL(quantile_finish_kernel, dim3(grid_for(QC, 256)), dim3(256),
+      0, stream, prefix, k1, cnt, le, next, QC, out_lo, out_hi);
+}
+
+void gdb_hip::launch_rle_expand_indices(
     const int64_t* runs, int64_t R, const uint8_t* blob, int bw,
     int32_t* out, int64_t n, hipStream_t stream) {
   hipLaunchKernelGGL(rle_expand_indices_kernel, dim3(grid_for(n, 256)),
                      dim3(256), 0, stream, runs, R, blob, bw, out, n);
 }
 
-void launch_gorilla_decode(
+void gdb_hip::launch_gorilla_decode(
     const uint8_t* blob, const int64_t* block_off, const int64_t* out_off,
     int64_t B, int64_t* out_ts, double* out_val, int64_t n,
     hipStream_t stream) {
@@ -1629,16 +1449,13 @@ void launch_gorilla_decode(
                      out_ts, out_val, n);
 }
 
-int gorilla_encode_max_block() { return GENC_MAX_BLOCK; }
-
-// `fail` must be zeroed by the caller; `vals` may be null (no value column).
-void launch_gorilla_scale(const double* vals, int64_t n, unsigned* fail,
-                          hipStream_t stream) {
+void gdb_hip::launch_gorilla_scale(const double* vals, int64_t n,
+                                   unsigned* fail, hipStream_t stream) {
   hipLaunchKernelGGL(gorilla_scale_kernel, dim3(grid_for(n, GENC_THREADS)),
                      dim3(GENC_THREADS), 0, stream, vals, n, fail);
 }
 
-void launch_gorilla_widths(
+void gdb_hip::launch_gorilla_widths(
     const int64_t* ts, const double* vals, int64_t n, int block, int pack_ts,
     const unsigned* fail, uint8_t* bits, int64_t* sizes, int64_t B,
     hipStream_t stream) {
@@ -1647,7 +1464,7 @@ void launch_gorilla_widths(
                      pack_ts, fail, bits, sizes);
 }
 
-void launch_gorilla_write(
+void gdb_hip::launch_gorilla_write(
     const int64_t* ts, const double* vals, int64_t n, int block,
     const unsigned* fail, const uint8_t* bits, const int64_t* block_off,
     uint8_t* blob, int64_t B, hipStream_t stream) {
@@ -1655,5 +1472,3 @@ void launch_gorilla_write(
                      dim3(GENC_THREADS), 0, stream, ts, vals, n, block, fail,
                      bits, block_off, blob);
 }
-
-}  // namespace gdb_hip

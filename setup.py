@@ -38,6 +38,7 @@ ext_modules = [
     CUDAExtension(
         "greptimedb_amd._hip_ops",
         sources=["csrc/hip_ops.cpp", "csrc/kernels.hip"],
+        depends=["csrc/kernels.h"],
         extra_compile_args={
             "cxx": ["-O3", "-std=c++17"],
             "nvcc": ["-O3", "-std=c++17", "--offload-arch=gfx950"],

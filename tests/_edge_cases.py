@@ -18,7 +18,7 @@ import torch
 
 import _oracles as orc
 
-AGG_TILE = 8192       # csrc/kernels.hip
+AGG_TILE = 8192       # csrc/kernels.h; tests/test_hip_ops_args.py compares
 LDS_CELLS = 1024
 GRID_SPAN = 2048 * 256  # threads of a capped grid: n above it loops twice
 
