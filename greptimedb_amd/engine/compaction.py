@@ -12,11 +12,8 @@ from __future__ import annotations
 
 import os
 
-import numpy as np
-import torch
-
+from greptimedb_amd.engine import merge
 from greptimedb_amd.engine import sst as sst_mod
-from greptimedb_amd.ops import dedup_mark_last, merge_last_non_null
 
 TRIGGER_FILE_NUM = 4
 MAX_INPUTS = 32
@@ -119,73 +116,22 @@ class Compactor:
     def _merge(self, region, fids: list[str]):
         batches = [region.sst_cache[f] for f in fids]
         device = region.device
-        ts = torch.cat([b.ts for b in batches])
-        se = torch.cat([b.series for b in batches])
-        # per-row sequences order rows across overlapping files; batches
-        # without one (pre-upgrade fixtures) get file-order synthetic seqs
-        seq_parts, synth_base = [], 0
-        for b in batches:
-            if b.seq is not None:
-                seq_parts.append(b.seq.to(torch.int64))
-                synth_base = max(synth_base, int(b.seq.max().item()) + 1 if b.n else 0)
-            else:
-                seq_parts.append(torch.arange(synth_base, synth_base + b.n,
-                                              dtype=torch.int64, device=device))
-                synth_base += b.n
-        seq = torch.cat(seq_parts)
-        # unify field layout
-        fnames = []
-        for b in batches:
-            for fn in b.field_names:
-                if fn not in fnames:
-                    fnames.append(fn)
-        n = ts.numel()
-        fields = torch.full((len(fnames), n), float("nan"), dtype=torch.float64,
-                            device=device)
-        off = 0
-        str_parts: dict[str, list] = {}
-        for b in batches:
-            for i, fn in enumerate(b.field_names):
-                fields[fnames.index(fn), off:off + b.n] = b.fields[i][: b.n]
-            for sn in getattr(b, "str_cols", {}):
-                str_parts.setdefault(sn, [])
-            off += b.n
-        # string columns (aligned, None-padded)
-        off = 0
-        for b in batches:
-            for sn in str_parts:
-                col = getattr(b, "str_cols", {}).get(sn)
-                if col is None:
-                    str_parts[sn].append(np.full(b.n, None, dtype=object))
-                else:
-                    str_parts[sn].append(np.asarray(col, dtype=object))
-            off += b.n
-        # sort by (series, ts, seq): stable sorts applied innermost-first so
-        # the newest (highest-seq) row of each (series, ts) group lands last
-        o0 = torch.argsort(seq, stable=True)
-        o1 = o0[torch.argsort(ts[o0], stable=True)]
-        perm = o1[torch.argsort(se[o1], stable=True)]
+        # per-row sequences order rows across overlapping files: sort by
+        # (series, ts, seq) so the newest row of each group lands last
+        ts, se, fields, seq, str_parts, fnames = merge.gather_rows(
+            batches, [b.seq for b in batches])
+        perm = merge.sort_perm(se, ts, seq)
         ts, se, seq = ts[perm], se[perm], seq[perm]
-        fields = fields[:, perm]
-        if region.merge_mode == "last_non_null":
-            from greptimedb_amd.engine.region import merge_str_last_non_null
-            kidx, fields = merge_last_non_null(se, ts, fields)
-            ts, se, seq = ts[kidx], se[kidx], seq[kidx]
+        mode = merge.region_mode(region)
+        kidx, fields = merge.merge_rows(se, ts, fields[:, perm], mode)
+        str_cols_sorted = {}
+        if str_parts:
             perm_h = perm.cpu().numpy()
-            kidx_h = kidx.cpu().numpy()
-            str_cols_sorted = {
-                sn: merge_str_last_non_null(kidx_h,
-                                            np.concatenate(parts)[perm_h])
-                for sn, parts in str_parts.items()}
-        else:
-            if not region.append_mode:
-                keep = dedup_mark_last(se.contiguous(), ts.contiguous())
-                kidx = keep.nonzero(as_tuple=True)[0]
-                ts, se, seq, fields = ts[kidx], se[kidx], seq[kidx], fields[:, kidx]
-                perm = perm[kidx]
-            perm_h = perm.cpu().numpy()
-            str_cols_sorted = {sn: np.concatenate(parts)[perm_h]
+            kidx_h = None if kidx is None else kidx.cpu().numpy()
+            str_cols_sorted = {sn: merge.merge_strs(mode, kidx_h, perm_h, parts)
                                for sn, parts in str_parts.items()}
+        if kidx is not None:
+            ts, se, seq = ts[kidx], se[kidx], seq[kidx]
 
         ts_h = ts.cpu().numpy()
         se_h = se.cpu().numpy()

@@ -7,15 +7,18 @@ f64[nf, cap]); row index == arrival (sequence) order, so "last wins" dedup
 is a stable sort away. 288 GB HBM3E makes a flat layout with generous
 preallocation the right call — no per-series pointer chasing on device.
 
-Appends are H2D copies at a row offset (torch.narrow().copy_), so ingest is
-one pinned-staging copy per column per batch. Sorting/dedup happen at scan
-or flush time on device.
+`append` copies one batch into the columns at the current row offset; the
+bulk ingest paths (engine.py write_regions_*) stage a routed batch once and
+scatter it into the regions' columns with the scatter_append kernel.
+Sorting and dedup happen at scan or flush time on device (engine/merge.py).
 """
 
 from __future__ import annotations
 
 import numpy as np
 import torch
+
+from greptimedb_amd.engine.merge import sort_perm
 
 
 class Memtable:
@@ -107,7 +110,5 @@ class Memtable:
         n = self.len
         ts = self.ts[:n]
         se = self.series[:n]
-        ord1 = torch.argsort(ts, stable=True)
-        ord2 = torch.argsort(se[ord1], stable=True)
-        perm = ord1[ord2]
+        perm = sort_perm(se, ts)
         return ts[perm], se[perm], self.fields[:, :n][:, perm], perm

@@ -16,12 +16,12 @@ import threading
 import numpy as np
 import torch
 
+from greptimedb_amd.engine import merge
 from greptimedb_amd.engine import sst as sst_mod
 from greptimedb_amd.engine.manifest import Manifest
 from greptimedb_amd.engine.memtable import Memtable
 from greptimedb_amd.engine.series import SeriesIndex
 from greptimedb_amd.models.schema import TableSchema
-from greptimedb_amd.ops import dedup_mark_last, merge_last_non_null
 
 
 class ScanSource:
@@ -43,19 +43,15 @@ class ScanSource:
         self.str_cols = str_cols or {}
         self.text_probe = text_probe
 
-
-def merge_str_last_non_null(kidx_h: np.ndarray, arr: np.ndarray) -> np.ndarray:
-    """Host half of the last_non_null merge for one string column: `arr`
-    is (series, ts, seq)-sorted, `kidx_h` the group-last rows; each group
-    yields its newest non-None value, or None when it has none."""
-    if len(kidx_h) == 0:
-        return arr[:0]
-    starts = np.concatenate(([0], kidx_h[:-1] + 1))
-    valid = np.fromiter((v is not None for v in arr), dtype=bool,
-                        count=len(arr))
-    cand = np.where(valid, np.arange(len(arr), dtype=np.int64), -1)
-    newest = np.maximum.reduceat(cand, starts)
-    return arr[np.where(newest >= 0, newest, kidx_h)]
+    def take_fields(self, idx, names) -> list:
+        """Rows `idx` (None: all n) of each named field, as f64 columns in
+        `names` order; a field this source lacks is a NaN column."""
+        rows = slice(self.n) if idx is None else idx
+        m = self.n if idx is None else idx.numel()
+        pos = [self.field_pos.get(fn) for fn in names]
+        return [self.fields[p][rows] if p is not None else
+                torch.full((m,), float("nan"), dtype=torch.float64,
+                           device=self.ts.device) for p in pos]
 
 
 class Region:
@@ -208,11 +204,7 @@ class Region:
                 t_f = torch.as_tensor(np.ascontiguousarray(fields)).to(dev)
                 t_seq = torch.as_tensor(seq).to(dev)
             # re-sort by (series, ts, seq): codes may differ from write-time order
-            ord1 = torch.argsort(t_seq, stable=True)
-            ord2 = torch.argsort(t_ts[ord1], stable=True)
-            perm = ord1[ord2]
-            ord3 = torch.argsort(t_se[perm], stable=True)
-            perm = perm[ord3]
+            perm = merge.sort_perm(t_se, t_ts, t_seq)
             batch = sst_mod.SstBatch(
                 t_ts[perm].contiguous(), t_se[perm].contiguous(),
                 t_f[:, perm].contiguous(), t_seq[perm].contiguous(),
@@ -362,36 +354,30 @@ class Region:
                 ft.reset_mem()  # new memtable rows start at 0
             entry = (mem, n, mem_postings, mem_base)
             self.flushing.append(entry)
+        # ties by arrival: a memtable's row index is its arrival order
         ts, se, fields, perm = mem.sorted_view()
-        kidx_h = None
-        if self.merge_mode == "last_non_null":
-            sorted_perm_h = perm.cpu().numpy()
-            kidx, fields = merge_last_non_null(se, ts, fields)
-            ts, se, perm = ts[kidx], se[kidx], perm[kidx]
-            kidx_h = kidx.cpu().numpy()
-        elif not self.append_mode:
-            keep = dedup_mark_last(se, ts)
-            idx = keep.nonzero(as_tuple=True)[0]
-            ts, se, fields, perm = ts[idx], se[idx], fields[:, idx], perm[idx]
-        seq_t = perm.to(torch.int64) + mem_base
-        ts_h = ts.cpu().numpy()
-        se_h = se.cpu().numpy()
-        f_h = fields.cpu().numpy()
-        perm_h = perm.cpu().numpy()
+        mode = merge.region_mode(self)
+        kidx, fields = merge.merge_rows(se, ts, fields, mode)
         # string columns: reorder host-side, build device posting segments
         str_cols_sorted: dict[str, np.ndarray] = {}
         text_index = {}
+        if mem.str_cols:
+            perm_h = perm.cpu().numpy()
+            kidx_h = None if kidx is None else kidx.cpu().numpy()
         for name, col in mem.str_cols.items():
-            if kidx_h is not None:
-                arr = merge_str_last_non_null(
-                    kidx_h, np.array(col[: n], dtype=object)[sorted_perm_h])
-            else:
-                arr = np.array(col[: n], dtype=object)[perm_h]
+            arr = merge.merge_strs(mode, kidx_h, perm_h,
+                                   [np.array(col[: n], dtype=object)])
             str_cols_sorted[name] = arr
             ft = self.text_cols.get(name)
             if ft is not None:
                 text_index[name] = ft.build_segment(list(arr), self.device)
-        seq_h = perm_h.astype(np.int64) + mem_base
+        if kidx is not None:
+            ts, se, perm = ts[kidx], se[kidx], perm[kidx]
+        seq_t = perm + mem_base
+        ts_h = ts.cpu().numpy()
+        se_h = se.cpu().numpy()
+        f_h = fields.cpu().numpy()
+        seq_h = seq_t.cpu().numpy()
         fid = sst_mod.new_file_id()
         path = os.path.join(self.dir, "sst", f"{fid}.parquet")
         meta = sst_mod.write_sst(path, self.schema, self.series.pks,
@@ -562,57 +548,22 @@ class Region:
         """last_non_null read path: gather the pruned sources, sort by
         (series, ts, seq) and merge each (series, ts) group field by field.
         A lone SST batch never gets here (flush and compaction leave it
-        group-unique). `seqs[i]` orders source i's rows: an SST's seq tensor,
-        a memtable's row-0 sequence, or None for a batch without sequences,
-        which gets file-order synthetic ones as compaction does. Nothing is
-        cached: every multi-source query re-merges its time range."""
-        device = self.device
-        total = sum(s.n for s in sources)
-        fields = torch.full((len(fnames), total), float("nan"),
-                            dtype=torch.float64, device=device)
-        seq_parts, synth_base, off = [], 0, 0
-        synth = any(q is None for q in seqs)
-        for s, q in zip(sources, seqs):
-            for fi, fn in enumerate(fnames):
-                pos = s.field_pos.get(fn)
-                if pos is not None and pos < s.fields.shape[0]:
-                    fields[fi, off:off + s.n] = s.fields[pos][: s.n]
-            if q is None:
-                q = torch.arange(synth_base, synth_base + s.n,
-                                 dtype=torch.int64, device=device)
-                synth_base += s.n
-            elif isinstance(q, int):
-                q = torch.arange(q, q + s.n, dtype=torch.int64, device=device)
-            else:
-                q = q.to(torch.int64)
-                if synth and s.n:
-                    synth_base = max(synth_base, int(q.max().item()) + 1)
-            seq_parts.append(q)
-            off += s.n
-        ts = torch.cat([s.ts[: s.n] for s in sources])
-        se = torch.cat([s.series[: s.n].to(torch.int32) for s in sources])
-        seq = torch.cat(seq_parts)
-        o0 = torch.argsort(seq, stable=True)
-        o1 = o0[torch.argsort(ts[o0], stable=True)]
-        perm = o1[torch.argsort(se[o1], stable=True)]
+        group-unique). `seqs` is merge.gather_rows' per-source sequence
+        argument. Nothing is cached: every multi-source query re-merges its
+        time range."""
+        ts, se, fields, seq, str_parts, _ = merge.gather_rows(
+            sources, seqs, fnames)
+        perm = merge.sort_perm(se, ts, seq)
         ts, se = ts[perm], se[perm]
-        kidx, merged = merge_last_non_null(se, ts, fields[:, perm])
-        str_names = []
-        for s in sources:
-            str_names.extend(k for k in s.str_cols if k not in str_names)
+        kidx, merged = merge.merge_rows(se, ts, fields[:, perm],
+                                        "last_non_null")
         str_cols = {}
-        if str_names:
+        if str_parts:
             perm_h = perm.cpu().numpy()
             kidx_h = kidx.cpu().numpy()
-            for name in str_names:
-                parts = []
-                for s in sources:
-                    col = s.str_cols.get(name)
-                    parts.append(np.full(s.n, None, dtype=object)
-                                 if col is None else
-                                 np.array(col[: s.n], dtype=object))
-                str_cols[name] = merge_str_last_non_null(
-                    kidx_h, np.concatenate(parts)[perm_h])
+            str_cols = {name: merge.merge_strs("last_non_null", kidx_h,
+                                               perm_h, parts)
+                        for name, parts in str_parts.items()}
         return ScanSource(ts[kidx].contiguous(), se[kidx].contiguous(),
                           merged, int(kidx.numel()),
                           {fn: i for i, fn in enumerate(fnames)},

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from greptimedb_amd.engine import sst as sst_mod
+from greptimedb_amd.engine.merge import sort_perm
 from greptimedb_amd.engine.region import Region
 from greptimedb_amd.engine.series import tsid_hash
 from greptimedb_amd.models.schema import region_id as make_region_id
@@ -75,8 +76,7 @@ def repartition_table(engine, name: str, n_new: int) -> int:
                 strs = {sn: np.asarray(col, dtype=object)[idx_h]
                         for sn, col in getattr(batch, "str_cols", {}).items()}
                 # sort by (series, ts) for the new region
-                o = torch.argsort(ts_t, stable=True)
-                perm = o[torch.argsort(se_t[o], stable=True)]
+                perm = sort_perm(se_t, ts_t)
                 ts_t, se_t, f_t = ts_t[perm], se_t[perm], f_t[:, perm]
                 perm_h = perm.cpu().numpy()
                 strs = {sn: a[perm_h] for sn, a in strs.items()}

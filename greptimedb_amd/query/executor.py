@@ -21,6 +21,8 @@ import numpy as np
 import torch
 
 from greptimedb_amd.engine.engine import MitoEngine, TableState
+from greptimedb_amd.engine.merge import (last_row_index, sort_last_rows,
+                                         sort_perm)
 from greptimedb_amd.models.schema import (
     ColumnSchema, DataType, SemanticType, TableSchema,
 )
@@ -29,7 +31,7 @@ from greptimedb_amd.query.parser import parse_sql
 from greptimedb_amd.utils.errors import (InvalidArguments, PlanQuery,
                                          TableAlreadyExists, TableNotFound)
 from greptimedb_amd.utils.timeutil import parse_ts_ms, trunc_unit_ms
-from greptimedb_amd.ops import ts_bucket_agg, dedup_mark_last
+from greptimedb_amd.ops import filter_series_time, ts_bucket_agg
 
 AGG_FUNCS = {"count", "sum", "min", "max", "avg", "mean", "last_value",
              "first_value"}
@@ -575,12 +577,10 @@ class Executor:
             lut_t = torch.as_tensor(lut, device=device) if lut is not None else None
             for fid in list(region.sst_cache.keys()):
                 b = region.sst_cache[fid]
-                src = type("S", (), {})()
                 from greptimedb_amd.engine.region import ScanSource
                 src = ScanSource(b.ts, b.series, b.fields, b.n,
                                  {fn: i for i, fn in enumerate(b.field_names)},
                                  True, getattr(b, "str_cols", {}), None)
-                from greptimedb_amd.ops import filter_series_time
                 del_mask = filter_series_time(b.ts, b.series, lut_t, ts_lo, ts_hi)
                 if plan.residual is not None:
                     del_mask &= self._eval_mask(plan.residual, src, region, device)
@@ -1694,7 +1694,6 @@ class Executor:
                     vt = torch.as_tensor(full).to(device)
                     if cache_holder is not None:
                         setattr(cache_holder, key, vt)
-                from greptimedb_amd.ops import filter_series_time
                 mask = filter_series_time(src.ts, src.series, lut_t, ts_lo, ts_hi)
                 if plan.residual is not None:
                     mask &= self._eval_mask(plan.residual, src, region, device)
@@ -2750,28 +2749,15 @@ class Executor:
 
         def source_cols(src):
             """(ts, series, fields aligned to agg_fields) after residual mask."""
-            ts_t, se_t = src.ts, src.series
-            sel_idx = None
+            ts_t, se_t, sel_idx = src.ts, src.series, None
             if plan.residual is not None:
                 mask = self._eval_mask(plan.residual, src, region, device)
                 sel_idx = mask.nonzero(as_tuple=True)[0]
-            rows = []
-            for fn in agg_fields:
-                p = src.field_pos.get(fn)
-                if p is None:
-                    rows.append(None)
-                else:
-                    rows.append(src.fields[p][: src.n])
-            if sel_idx is not None:
                 ts_t = ts_t[sel_idx].contiguous()
                 se_t = se_t[sel_idx].contiguous()
-                rows = [r[sel_idx] if r is not None else None for r in rows]
             m = ts_t.numel()
-            f_t = torch.stack([
-                r if r is not None else
-                torch.full((m,), float("nan"), dtype=torch.float64, device=device)
-                for r in rows]) if nf else torch.zeros((1, max(m, 1)), dtype=torch.float64,
-                                                       device=device)
+            f_t = torch.stack(src.take_fields(sel_idx, agg_fields)) if nf else \
+                torch.zeros((1, max(m, 1)), dtype=torch.float64, device=device)
             return ts_t, se_t, f_t.contiguous()
 
         fidx_t = torch.arange(nf, dtype=torch.int32, device=device) if nf else \
@@ -2794,8 +2780,8 @@ class Executor:
                     continue
                 if single:
                     # one source, merge-mode: dedup within it
-                    ts_t, se_t, f_t = _sort_dedup(ts_t, se_t, f_t)
-                yield ts_t, se_t, f_t, fidx_t
+                    ts_t, se_t, f_t, _, _ = sort_last_rows(se_t, ts_t, f_t)
+                yield ts_t, se_t, f_t.contiguous(), fidx_t
             return
         # merge-mode, multiple sources: gather + global dedup
         cols = [source_cols(s) for s in sources]
@@ -2805,8 +2791,8 @@ class Executor:
         ts_t = torch.cat([c[0] for c in cols])
         se_t = torch.cat([c[1] for c in cols])
         f_t = torch.cat([c[2] for c in cols], dim=1)
-        ts_t, se_t, f_t = _sort_dedup(ts_t, se_t, f_t)
-        yield ts_t, se_t, f_t, fidx_t
+        ts_t, se_t, f_t, _, _ = sort_last_rows(se_t, ts_t, f_t)
+        yield ts_t, se_t, f_t.contiguous(), fidx_t
 
     def _finalize_agg(self, sel, plan, group_keys, origin, bucket_ms,
                       agg_fields, sums, cnts, mins, maxs, rowcnt,
@@ -2934,8 +2920,6 @@ class Executor:
         cols = [c[keep_idx] for c in cols]
         return QueryResult(names, cols, kinds)
 
-    # ------------------------------------------------------ raw path
-
     # ------------------------------------------------------ RANGE queries
 
     _RANGE_MODES = {"min": 6, "max": 7, "sum": 5, "avg": 4, "mean": 4,
@@ -2949,7 +2933,7 @@ class Executor:
         sample streams sorted by (slot, ts) feed the prom_range_eval window
         kernel with te = t + range - 1 (integer-ms shift turns the kernel's
         (tb, te] window into [t, t+range))."""
-        from greptimedb_amd.ops import filter_series_time, prom_range_eval
+        from greptimedb_amd.ops import prom_range_eval
         st = plan.table
         device = self.engine.config.device
         schema = st.schema
@@ -2976,6 +2960,7 @@ class Executor:
                 raise PlanQuery(f"RANGE aggregate needs a column arg: {f.name}")
             calls.append((nd, fname, arg))
         fields = sorted({arg for _nd, _f, arg in calls})
+        col_fields = [fn for fn in fields if fn != ts_name]
 
         gt = sel.align_by if sel.align_by is not None else \
             [c.name for c in schema.tag_columns]
@@ -2998,15 +2983,9 @@ class Executor:
                 idx = mask.nonzero(as_tuple=True)[0]
                 if idx.numel() == 0:
                     continue
-                fv = {}
-                for fn in fields:
-                    if fn == ts_name:
-                        fv[fn] = src.ts[idx].double()
-                        continue
-                    p = src.field_pos.get(fn)
-                    fv[fn] = src.fields[p][idx] if p is not None else \
-                        torch.full((idx.numel(),), float("nan"),
-                                   dtype=torch.float64, device=device)
+                fv = dict(zip(col_fields, src.take_fields(idx, col_fields)))
+                if ts_name in fields:
+                    fv[ts_name] = src.ts[idx].double()
                 chunks.append((src.ts[idx], src.series[idx], fv))
             if not chunks:
                 continue
@@ -3014,12 +2993,10 @@ class Executor:
             se_t = torch.cat([c[1] for c in chunks])
             fv = {fn: torch.cat([c[2][fn] for c in chunks]) for fn in fields}
             if not st.append_mode:   # last-wins dedup on (series, ts)
-                o2 = torch.argsort(ts_t, stable=True)
-                p2 = o2[torch.argsort(se_t[o2], stable=True)]
+                p2 = sort_perm(se_t, ts_t)
                 ts_t, se_t = ts_t[p2], se_t[p2]
                 fv = {fn: v[p2] for fn, v in fv.items()}
-                keep = dedup_mark_last(se_t.int().contiguous(), ts_t.contiguous())
-                kidx = keep.nonzero(as_tuple=True)[0]
+                kidx = last_row_index(se_t, ts_t)
                 if kidx.numel() != ts_t.numel():
                     ts_t, se_t = ts_t[kidx], se_t[kidx]
                     fv = {fn: v[kidx] for fn, v in fv.items()}
@@ -3035,8 +3012,7 @@ class Executor:
         if parts:
             ts_all = torch.cat([p[0] for p in parts])
             sl_all = torch.cat([p[1] for p in parts])
-            o = torch.argsort(ts_all, stable=True)
-            perm = o[torch.argsort(sl_all[o], stable=True)]
+            perm = sort_perm(sl_all, ts_all)
             ts_all, sl_all = ts_all[perm], sl_all[perm]
             fvals = {fn: torch.cat([p[2][fn] for p in parts])[perm]
                      for fn in fields}
@@ -3282,8 +3258,7 @@ class Executor:
                 lut[cand] = 1
             lut_t = torch.as_tensor(lut, device=device) if lut is not None else None
             chunks = []
-            for si, src in enumerate(region.scan_sources(ts_lo, ts_hi)):
-                from greptimedb_amd.ops import filter_series_time
+            for src in region.scan_sources(ts_lo, ts_hi):
                 mask = filter_series_time(src.ts, src.series, lut_t, ts_lo, ts_hi)
                 if plan.residual is not None:
                     mask &= self._eval_mask(plan.residual, src, region, device)
@@ -3292,14 +3267,7 @@ class Executor:
                     continue
                 ts_t = src.ts[idx]
                 se_t = src.series[idx]
-                f_rows = []
-                for fn in needed_fields:
-                    p = src.field_pos.get(fn)
-                    if p is None:
-                        f_rows.append(torch.full((idx.numel(),), float("nan"),
-                                                 dtype=torch.float64, device=device))
-                    else:
-                        f_rows.append(src.fields[p][idx])
+                f_rows = src.take_fields(idx, needed_fields)
                 f_t = torch.stack(f_rows) if f_rows else torch.zeros((0, idx.numel()), device=device)
                 s_vals = {}
                 if needed_strs:
@@ -3319,15 +3287,9 @@ class Executor:
                 torch.zeros((0, ts_t.numel()), device=device)
             s_cols = {sn: np.concatenate([c[3][sn] for c in chunks])
                       for sn in needed_strs}
-            if not st.append_mode and len(chunks) >= 1:
+            if not st.append_mode:
                 # sort by (series, ts, arrival) then keep last
-                o2 = torch.argsort(ts_t, stable=True)
-                perm = o2[torch.argsort(se_t[o2], stable=True)]
-                ts_t, se_t = ts_t[perm], se_t[perm]
-                f_t = f_t[:, perm]
-                keep = dedup_mark_last(se_t.contiguous(), ts_t.contiguous())
-                kidx = keep.nonzero(as_tuple=True)[0]
-                ts_t, se_t, f_t = ts_t[kidx], se_t[kidx], f_t[:, kidx]
+                ts_t, se_t, f_t, perm, kidx = sort_last_rows(se_t, ts_t, f_t)
                 if needed_strs:
                     sel_h = perm[kidx].cpu().numpy()
                     s_cols = {sn: v[sel_h] for sn, v in s_cols.items()}
@@ -3571,17 +3533,6 @@ class Executor:
 
 
 # ------------------------------------------------------------------ helpers
-
-
-def _sort_dedup(ts_t, se_t, f_t):
-    """Stable sort by (series, ts, arrival); keep last of each (series, ts)."""
-    o2 = torch.argsort(ts_t, stable=True)
-    perm = o2[torch.argsort(se_t[o2], stable=True)]
-    ts_t, se_t, f_t = ts_t[perm], se_t[perm], f_t[:, perm]
-    keep = dedup_mark_last(se_t.contiguous(), ts_t.contiguous())
-    kidx = keep.nonzero(as_tuple=True)[0]
-    return (ts_t[kidx].contiguous(), se_t[kidx].contiguous(),
-            f_t[:, kidx].contiguous())
 
 
 def _py_cmp(op, a, b):

@@ -20,7 +20,8 @@ import re as _re
 import numpy as np
 import torch
 
-from greptimedb_amd.ops import dedup_mark_last, prom_range_eval
+from greptimedb_amd.engine.merge import last_row_index, sort_perm
+from greptimedb_amd.ops import filter_series_time, prom_range_eval
 from greptimedb_amd.ops.cpu_ref import PROM_MODES
 from greptimedb_amd.query.promql import ast
 from greptimedb_amd.query.promql.parser import parse_promql
@@ -622,7 +623,6 @@ class PromEvaluator:
                 p = src.field_pos.get(field)
                 if p is None:
                     continue
-                from greptimedb_amd.ops import filter_series_time
                 mask = filter_series_time(src.ts, src.series,
                                           lut_t if codes is not None else None, lo, hi)
                 idx = mask.nonzero(as_tuple=True)[0]
@@ -644,11 +644,9 @@ class PromEvaluator:
             # monotone in code, so a single (series, ts)-sorted source is
             # already slot-sorted — skip the sort (the common SST-cache case).
             if not (len(chunks) == 1 and all_sorted):
-                o = torch.argsort(ts_t, stable=True)
-                perm = o[torch.argsort(slots[o], stable=True)]
+                perm = sort_perm(slots, ts_t)
                 ts_t, slots, v_t = ts_t[perm], slots[perm], v_t[perm]
-            keep = dedup_mark_last(slots.int().contiguous(), ts_t.contiguous())
-            kidx = keep.nonzero(as_tuple=True)[0]
+            kidx = last_row_index(slots, ts_t)
             if kidx.numel() != ts_t.numel():
                 ts_t, slots, v_t = ts_t[kidx], slots[kidx], v_t[kidx]
             parts.append((ts_t, slots))
