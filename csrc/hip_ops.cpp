@@ -513,6 +513,27 @@ torch::Tensor bucket_cells(
   return cell;
 }
 
+// One (cell i32[n], fields f64[nf_total, >=n], field_idx i32[nf]) source of
+// the grouped ops below, against the first source's cell tensor.
+static void check_cell_source(const torch::Tensor& cell,
+                              const torch::Tensor& fields,
+                              const torch::Tensor& fidx,
+                              const torch::Tensor& first) {
+  check_arg(cell, "cell", torch::kInt32, first);
+  check_arg(fidx, "field_idx", torch::kInt32, first);
+  TORCH_CHECK(cell.dim() == 1 && fidx.dim() == 1);
+  // fields may be a row-strided view (a memtable's used prefix), so it is
+  // the one tensor that does not go through check_arg
+  TORCH_CHECK(fields.is_cuda() && fields.device() == first.device(),
+              "fields must be a GPU tensor on the first source's device");
+  TORCH_CHECK(fields.scalar_type() == torch::kFloat64 && fields.dim() == 2);
+  TORCH_CHECK(fields.size(1) >= cell.numel(), "fields shorter than rows");
+  TORCH_CHECK(fields.size(1) <= 1 || fields.stride(1) == 1,
+              "fields must have unit stride along rows");
+  TORCH_CHECK(fields.size(0) <= 1 || fields.stride(0) >= fields.size(1),
+              "fields rows overlap");
+}
+
 // Exact grouped order statistics (K21). sources: (cell i32[n], fields
 // f64[nf_total, >=n] with unit inner stride, field_idx i32[nf]) triples that
 // accumulate into one state; selection s reads field row
@@ -549,20 +570,7 @@ std::vector<torch::Tensor> grouped_quantile(
     auto& cell = std::get<0>(src);
     auto& fields = std::get<1>(src);
     auto& fidx = std::get<2>(src);
-    const torch::Tensor& first = std::get<0>(sources.front());
-    check_arg(cell, "cell", torch::kInt32, first);
-    check_arg(fidx, "field_idx", torch::kInt32, first);
-    TORCH_CHECK(cell.dim() == 1 && fidx.dim() == 1);
-    // fields may be a row-strided view (a memtable's used prefix), so it is
-    // the one tensor that does not go through check_arg
-    TORCH_CHECK(fields.is_cuda() && fields.device() == first.device(),
-                "fields must be a GPU tensor on the first source's device");
-    TORCH_CHECK(fields.scalar_type() == torch::kFloat64 && fields.dim() == 2);
-    TORCH_CHECK(fields.size(1) >= cell.numel(), "fields shorter than rows");
-    TORCH_CHECK(fields.size(1) <= 1 || fields.stride(1) == 1,
-                "fields must have unit stride along rows");
-    TORCH_CHECK(fields.size(0) <= 1 || fields.stride(0) >= fields.size(1),
-                "fields rows overlap");
+    check_cell_source(cell, fields, fidx, std::get<0>(sources.front()));
     for (int64_t f : field_of_sel)
       TORCH_CHECK(f >= 0 && f < fidx.numel(), "field_of_sel ", f,
                   " outside field_idx of length ", fidx.numel());
@@ -643,6 +651,135 @@ std::vector<torch::Tensor> grouped_quantile(
   return {lo, hi, cnt};
 }
 
+// Grouped second moments (K22) in two passes with no host synchronisation.
+// sources as for grouped_quantile; selection s pairs field rows
+// field_idx[fx_of_sel[s]] and field_idx[fy_of_sel[s]] (fx == fy: one column).
+// A row counts in its cell where neither value is NaN. Returns, each
+// [M, n_cells]: n i64, mean_x, mean_y, m2x, m2y, cxy f64, const_x, const_y
+// bool. m2 = sum (x - mean)^2 and cxy = sum (x - mean_x)(y - mean_y) over
+// the counted rows; const = min == max over them, and then m2 (and cxy) is
+// exactly 0. n == 0: NaN means, zero sums, flags clear. As in
+// grouped_quantile, a field_idx VALUE outside fields makes the kernels skip
+// that selection for that source. lds_cells caps the cell span a tile may
+// have to accumulate in LDS (clamped to LDS_CELLS); 0 forces global atomics.
+std::vector<torch::Tensor> grouped_moments(
+    std::vector<std::tuple<torch::Tensor, torch::Tensor, torch::Tensor>> sources,
+    std::vector<int64_t> fx_of_sel, std::vector<int64_t> fy_of_sel,
+    int64_t n_cells, int64_t lds_cells) {
+  TORCH_CHECK(lds_cells >= 0, "lds_cells must not be negative");
+  const int64_t M = (int64_t)fx_of_sel.size();
+  TORCH_CHECK(M >= 1, "grouped_moments needs at least one selection");
+  TORCH_CHECK((int64_t)fy_of_sel.size() == M, "fx_of_sel and fy_of_sel differ in length");
+  TORCH_CHECK(n_cells >= 1, "n_cells must be positive");
+  TORCH_CHECK(n_cells <= kMaxQuantileCells && M * n_cells <= kMaxQuantileCells,
+              "grouped_moments: M * n_cells = ", M, " * ", n_cells,
+              " exceeds ", kMaxQuantileCells);
+  int64_t total_rows = 0;
+  torch::Device dev(torch::kCPU);
+  for (auto& src : sources) {
+    auto& cell = std::get<0>(src);
+    auto& fidx = std::get<2>(src);
+    check_cell_source(cell, std::get<1>(src), fidx, std::get<0>(sources.front()));
+    for (int64_t s = 0; s < M; s++)
+      TORCH_CHECK(fx_of_sel[s] >= 0 && fx_of_sel[s] < fidx.numel() &&
+                  fy_of_sel[s] >= 0 && fy_of_sel[s] < fidx.numel(),
+                  "selection (", fx_of_sel[s], ", ", fy_of_sel[s],
+                  ") outside field_idx of length ", fidx.numel());
+    total_rows += cell.numel();
+    dev = cell.device();
+  }
+  TORCH_CHECK(sources.empty() || dev.is_cuda());
+  if (sources.empty()) dev = torch::Device(torch::kCUDA, at::cuda::current_device());
+  auto o_f64 = torch::TensorOptions().dtype(torch::kFloat64).device(dev);
+  auto o_i64 = o_f64.dtype(torch::kInt64);
+  auto o_bool = o_f64.dtype(torch::kBool);
+  auto cnt = torch::zeros({M, n_cells}, o_i64);
+  auto m2x = torch::zeros({M, n_cells}, o_f64);
+  auto m2y = torch::zeros({M, n_cells}, o_f64);
+  auto cxy = torch::zeros({M, n_cells}, o_f64);
+  if (total_rows == 0) {
+    auto nan = torch::full({M, n_cells}, std::nan(""), o_f64);
+    auto no = torch::zeros({M, n_cells}, o_bool);
+    return {cnt, nan, nan.clone(), m2x, m2y, cxy, no, no.clone()};
+  }
+  auto sx = torch::zeros({M, n_cells}, o_f64);
+  auto sy = torch::zeros({M, n_cells}, o_f64);
+  auto minx = torch::full({M, n_cells}, -1, o_i64);     // u64 max
+  auto maxx = torch::zeros({M, n_cells}, o_i64);
+  auto miny = torch::full({M, n_cells}, -1, o_i64);
+  auto maxy = torch::zeros({M, n_cells}, o_i64);
+  auto mean_x = torch::empty({M, n_cells}, o_f64);
+  auto mean_y = torch::empty({M, n_cells}, o_f64);
+  auto const_x = torch::empty({M, n_cells}, o_bool);
+  auto const_y = torch::empty({M, n_cells}, o_bool);
+  std::vector<int32_t> sel32(2 * M);
+  std::vector<int64_t> same;                    // selections with x == y
+  for (int64_t s = 0; s < M; s++) {
+    sel32[s] = (int32_t)fx_of_sel[s];
+    sel32[M + s] = (int32_t)fy_of_sel[s];
+    if (fx_of_sel[s] == fy_of_sel[s]) same.push_back(s);
+  }
+  auto sel_d = torch::from_blob(sel32.data(), {2 * M}, torch::kInt32).to(dev);
+  const int32_t* fx_p = sel_d.data_ptr<int32_t>();
+  const int32_t* fy_p = fx_p + M;
+  auto stream = at::cuda::getCurrentHIPStream().stream();
+  auto u64 = [](torch::Tensor& t) {
+    return reinterpret_cast<unsigned long long*>(t.data_ptr<int64_t>());
+  };
+  auto check = [](const char* what) {
+    const hipError_t err = hipGetLastError();
+    TORCH_CHECK(err == hipSuccess, what, " launch failed: ", hipGetErrorString(err));
+  };
+  auto field_stride = [](const torch::Tensor& f) {
+    return f.size(0) > 1 ? f.stride(0) : f.size(1);
+  };
+  const int lds_cap = (int)std::min<int64_t>(lds_cells, gdb_hip::LDS_CELLS);
+  for (auto& src : sources) {
+    auto& cell = std::get<0>(src);
+    auto& fields = std::get<1>(src);
+    auto& fidx = std::get<2>(src);
+    if (cell.numel() == 0) continue;
+    gdb_hip::launch_moments_sums(
+        cell.data_ptr<int32_t>(), fields.data_ptr<double>(), field_stride(fields),
+        fidx.data_ptr<int32_t>(), (int)fields.size(0), fx_p, fy_p, (int)M,
+        cell.numel(), (int)n_cells, lds_cap, u64(cnt), sx.data_ptr<double>(),
+        sy.data_ptr<double>(), u64(minx), u64(maxx), u64(miny), u64(maxy),
+        stream);
+    check("moments_sums");
+  }
+  gdb_hip::launch_moments_mean(
+      u64(cnt), sx.data_ptr<double>(), sy.data_ptr<double>(), u64(minx),
+      u64(maxx), u64(miny), u64(maxy), fx_p, fy_p, (int)n_cells, M * n_cells,
+      mean_x.data_ptr<double>(), mean_y.data_ptr<double>(),
+      const_x.data_ptr<bool>(), const_y.data_ptr<bool>(), stream);
+  check("moments_mean");
+  for (auto& src : sources) {
+    auto& cell = std::get<0>(src);
+    auto& fields = std::get<1>(src);
+    auto& fidx = std::get<2>(src);
+    if (cell.numel() == 0) continue;
+    gdb_hip::launch_moments_centred(
+        cell.data_ptr<int32_t>(), fields.data_ptr<double>(), field_stride(fields),
+        fidx.data_ptr<int32_t>(), (int)fields.size(0), fx_p, fy_p, (int)M,
+        cell.numel(), (int)n_cells, lds_cap, mean_x.data_ptr<double>(),
+        mean_y.data_ptr<double>(), m2x.data_ptr<double>(),
+        m2y.data_ptr<double>(), cxy.data_ptr<double>(), stream);
+    check("moments_centred");
+  }
+  // one-argument selections filled only the x planes
+  if (!same.empty()) {
+    auto idx = torch::from_blob(same.data(), {(int64_t)same.size()}, torch::kInt64).to(dev);
+    auto one = m2x.index_select(0, idx);
+    m2y.index_copy_(0, idx, one);
+    cxy.index_copy_(0, idx, one);
+  }
+  // a constant column has x - mean == 0 in every row unless it is infinite
+  m2x.masked_fill_(const_x, 0.0);
+  m2y.masked_fill_(const_y, 0.0);
+  cxy.masked_fill_(const_x.logical_or(const_y), 0.0);
+  return {cnt, mean_x, mean_y, m2x, m2y, cxy, const_x, const_y};
+}
+
 // {tile rows, LDS cell capacity, grid cap} of the selection kernels.
 std::vector<int64_t> quantile_launch_config() {
   return {gdb_hip::QSEL_TILE, gdb_hip::QSEL_LDS_CELLS, gdb_hip::QSEL_MAX_GRID};
@@ -681,6 +818,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("sources"), py::arg("field_of_sel"), py::arg("p_of_sel"),
         py::arg("n_cells"), py::arg("on_pass") = py::none(),
         py::arg("lds_cells") = 16);
+  m.def("grouped_moments", &grouped_moments,
+        "grouped variance / covariance planes in two passes (K22)",
+        py::arg("sources"), py::arg("fx_of_sel"), py::arg("fy_of_sel"),
+        py::arg("n_cells"), py::arg("lds_cells") = gdb_hip::LDS_CELLS);
   m.def("quantile_launch_config", &quantile_launch_config,
         "tile rows, LDS cell capacity and grid cap of the selection kernels");
 }

@@ -101,6 +101,29 @@ void launch_quantile_finish(
     const unsigned long long* le, const unsigned long long* next, int64_t QC,
     double* out_lo, double* out_hi, hipStream_t stream);
 
+// grouped moments: planes are [M, n_cells]; min keys start at u64 max, every
+// other accumulator at 0; n >= 1; lds_cap is clamped to LDS_CELLS
+void launch_moments_sums(
+    const int32_t* cell, const double* fields, int64_t field_stride,
+    const int32_t* field_idx, int n_field_rows, const int32_t* fx_of_sel,
+    const int32_t* fy_of_sel, int M, int64_t n, int n_cells, int lds_cap,
+    unsigned long long* cnt, double* sx, double* sy,
+    unsigned long long* minx, unsigned long long* maxx,
+    unsigned long long* miny, unsigned long long* maxy, hipStream_t stream);
+void launch_moments_mean(
+    const unsigned long long* cnt, const double* sx, const double* sy,
+    const unsigned long long* minx, const unsigned long long* maxx,
+    const unsigned long long* miny, const unsigned long long* maxy,
+    const int32_t* fx_of_sel, const int32_t* fy_of_sel, int n_cells,
+    int64_t MC, double* mean_x, double* mean_y, bool* const_x, bool* const_y,
+    hipStream_t stream);
+void launch_moments_centred(
+    const int32_t* cell, const double* fields, int64_t field_stride,
+    const int32_t* field_idx, int n_field_rows, const int32_t* fx_of_sel,
+    const int32_t* fy_of_sel, int M, int64_t n, int n_cells, int lds_cap,
+    const double* mean_x, const double* mean_y, double* m2x, double* m2y,
+    double* cxy, hipStream_t stream);
+
 void launch_scatter_append(
     const int64_t* ts, const int32_t* series, const double* fields,
     const int32_t* region_of, const int64_t* dst_off,

@@ -17,6 +17,8 @@
 //  - prom_range_eval_kernel : K7/K8 PromQL selector and range functions.
 //  - quantile_{hist,pick,next,finish}_kernel : K21 exact grouped order
 //    statistics by radix-histogram selection over bucket cells.
+//  - moments_{sums,mean,centred}_kernel : K22 grouped second moments
+//    (variance, covariance, correlation) in two passes over bucket cells.
 //  - scatter_append_kernel / scatter_append_packed_kernel : K16 routed
 //    ingest batch -> region memtables.
 //  - rle_expand_indices_kernel : K11 parquet hybrid RLE/bit-packed indices.
@@ -862,6 +864,285 @@ __global__ void quantile_finish_kernel(
   }
 }
 
+// ------------------------------------------- K22 grouped two-pass moments
+//
+// Second moments per (selection, cell): a selection is a pair of field
+// columns (x, y), x == y being the one-argument form; a row counts where its
+// cell is valid and neither value is NaN (pairwise deletion). Two streaming
+// passes in the shape of field_bucket_agg_lds_kernel (AGG_TILE-row tiles,
+// coalesced loads, the tile's cell span privatised in LDS, global atomics
+// when the span exceeds lds_cap), one selection at a time:
+//   moments_sums_kernel    : pair count, sum x, sum y, min/max keys of x, y
+//   moments_mean_kernel    : means and the exact constant flags, per cell
+//   moments_centred_kernel : sum (x-mx)^2, sum (y-my)^2, sum (x-mx)(y-my)
+// Summing squares of raw values would cancel catastrophically for data far
+// from zero; centring on the mean of pass 1 keeps every term small.
+// LDS: pass 1 holds a u32 count and six 8-byte tables (52 KiB, three blocks
+// per CU inside 160 KiB), pass 2 a u32 count and three f64 tables (28 KiB).
+// A selection with x == y reads one column and fills only the x planes; the
+// binding copies them to the y planes.
+// Cell ids outside [0, n_cells) are skipped like -1.
+
+// The tile's span of valid cell ids through s_lo/s_hi; false when no row of
+// the tile is kept. Every thread of the block must call it.
+DEV_INLINE bool moments_tile_span(const int32_t* __restrict__ cell, int64_t t0,
+                                  int64_t t1, int n_cells, int32_t* s_lo,
+                                  int32_t* s_hi, int32_t& lo, int32_t& hi) {
+  const int tid = threadIdx.x;
+  if (tid == 0) { *s_lo = INT32_MAX; *s_hi = -1; }
+  __syncthreads();
+  int32_t my_lo = INT32_MAX, my_hi = -1;
+  for (int64_t i = t0 + tid; i < t1; i += blockDim.x) {
+    const int32_t c = cell[i];
+    if (c >= 0 && c < n_cells) { my_lo = min(my_lo, c); my_hi = max(my_hi, c); }
+  }
+  if (my_hi >= 0) {
+    atomicMin(s_lo, my_lo);
+    atomicMax(s_hi, my_hi);
+  }
+  __syncthreads();
+  lo = *s_lo;
+  hi = *s_hi;
+  __syncthreads();
+  return hi >= 0;
+}
+
+// Order key of a value for the constant test: -0.0 and 0.0 compare equal as
+// numbers, so both take the key of 0.0.
+DEV_INLINE unsigned long long moments_key(double v) {
+  return (unsigned long long)f64_to_key(v == 0.0 ? 0.0 : v);
+}
+
+// Planes are [M, n_cells]; min keys start at u64 max, everything else at 0.
+__global__ void __launch_bounds__(256) moments_sums_kernel(
+    const int32_t* __restrict__ cell,
+    const double* __restrict__ fields, int64_t field_stride,
+    const int32_t* __restrict__ field_idx, int n_field_rows,
+    const int32_t* __restrict__ fx_of_sel, const int32_t* __restrict__ fy_of_sel,
+    int M, int64_t n, int n_cells, int lds_cap,
+    unsigned long long* __restrict__ out_n,
+    double* __restrict__ out_sx, double* __restrict__ out_sy,
+    unsigned long long* __restrict__ out_minx,
+    unsigned long long* __restrict__ out_maxx,
+    unsigned long long* __restrict__ out_miny,
+    unsigned long long* __restrict__ out_maxy) {
+  __shared__ int32_t s_lo, s_hi;
+  __shared__ unsigned int s_cnt[LDS_CELLS];
+  __shared__ double s_sx[LDS_CELLS];
+  __shared__ double s_sy[LDS_CELLS];
+  __shared__ unsigned long long s_minx[LDS_CELLS];
+  __shared__ unsigned long long s_maxx[LDS_CELLS];
+  __shared__ unsigned long long s_miny[LDS_CELLS];
+  __shared__ unsigned long long s_maxy[LDS_CELLS];
+  const int tid = threadIdx.x;
+  const int nthreads = blockDim.x;
+  const int64_t ntiles = (n + AGG_TILE - 1) / AGG_TILE;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t t0 = tile * AGG_TILE;
+    const int64_t t1 = min(t0 + (int64_t)AGG_TILE, n);
+    int32_t lo, hi;
+    if (!moments_tile_span(cell, t0, t1, n_cells, &s_lo, &s_hi, lo, hi)) continue;
+    const int range = hi - lo + 1;
+    const bool in_lds = range <= lds_cap;
+    for (int s = 0; s < M; s++) {
+      const int32_t rx = field_idx[fx_of_sel[s]];
+      const int32_t ry = field_idx[fy_of_sel[s]];
+      if (rx < 0 || rx >= n_field_rows || ry < 0 || ry >= n_field_rows)
+        continue;                                          // block-uniform
+      const bool same = fx_of_sel[s] == fy_of_sel[s];
+      const double* __restrict__ colx = fields + (int64_t)rx * field_stride;
+      const double* __restrict__ coly = fields + (int64_t)ry * field_stride;
+      const int64_t sbase = (int64_t)s * n_cells;
+      if (in_lds) {
+        for (int k = tid; k < range; k += nthreads) {
+          s_cnt[k] = 0u; s_sx[k] = 0.0; s_sy[k] = 0.0;
+          s_minx[k] = ~0ULL; s_maxx[k] = 0ULL;
+          s_miny[k] = ~0ULL; s_maxy[k] = 0ULL;
+        }
+        __syncthreads();
+        for (int64_t i = t0 + tid; i < t1; i += nthreads) {
+          const int32_t c = cell[i];
+          if (c < 0 || c >= n_cells) continue;
+          const double x = colx[i];
+          const double y = same ? x : coly[i];
+          if (isnan(x) || isnan(y)) continue;
+          const int k = c - lo;
+          atomicAdd(&s_cnt[k], 1u);
+          atomicAdd(&s_sx[k], x);
+          const unsigned long long kx = moments_key(x);
+          atomicMin(&s_minx[k], kx);
+          atomicMax(&s_maxx[k], kx);
+          if (!same) {
+            atomicAdd(&s_sy[k], y);
+            const unsigned long long ky = moments_key(y);
+            atomicMin(&s_miny[k], ky);
+            atomicMax(&s_maxy[k], ky);
+          }
+        }
+        __syncthreads();
+        for (int k = tid; k < range; k += nthreads) {
+          if (!s_cnt[k]) continue;
+          const int64_t o = sbase + lo + k;
+          atomicAdd(&out_n[o], (unsigned long long)s_cnt[k]);
+          atomicAdd(&out_sx[o], s_sx[k]);
+          atomicMin(&out_minx[o], s_minx[k]);
+          atomicMax(&out_maxx[o], s_maxx[k]);
+          if (!same) {
+            atomicAdd(&out_sy[o], s_sy[k]);
+            atomicMin(&out_miny[o], s_miny[k]);
+            atomicMax(&out_maxy[o], s_maxy[k]);
+          }
+        }
+        __syncthreads();
+      } else {
+        for (int64_t i = t0 + tid; i < t1; i += nthreads) {
+          const int32_t c = cell[i];
+          if (c < 0 || c >= n_cells) continue;
+          const double x = colx[i];
+          const double y = same ? x : coly[i];
+          if (isnan(x) || isnan(y)) continue;
+          const int64_t o = sbase + c;
+          atomicAdd(&out_n[o], 1ULL);
+          atomicAdd(&out_sx[o], x);
+          const unsigned long long kx = moments_key(x);
+          atomicMin(&out_minx[o], kx);
+          atomicMax(&out_maxx[o], kx);
+          if (!same) {
+            atomicAdd(&out_sy[o], y);
+            const unsigned long long ky = moments_key(y);
+            atomicMin(&out_miny[o], ky);
+            atomicMax(&out_maxy[o], ky);
+          }
+        }
+      }
+    }
+  }
+}
+
+// Means and constant flags of every (selection, cell), after the last source
+// of pass 1. A constant column's mean is the value itself, not sum / n, so
+// that pass 2 sees x - mean == 0 exactly. n == 0: NaN means, flags clear.
+__global__ void moments_mean_kernel(
+    const unsigned long long* __restrict__ cnt,
+    const double* __restrict__ sx, const double* __restrict__ sy,
+    const unsigned long long* __restrict__ minx,
+    const unsigned long long* __restrict__ maxx,
+    const unsigned long long* __restrict__ miny,
+    const unsigned long long* __restrict__ maxy,
+    const int32_t* __restrict__ fx_of_sel, const int32_t* __restrict__ fy_of_sel,
+    int n_cells, int64_t MC,
+    double* __restrict__ mean_x, double* __restrict__ mean_y,
+    bool* __restrict__ const_x, bool* __restrict__ const_y) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < MC; i += stride) {
+    const unsigned long long c = cnt[i];
+    if (c == 0) {
+      mean_x[i] = quiet_nan(); mean_y[i] = quiet_nan();
+      const_x[i] = false; const_y[i] = false;
+      continue;
+    }
+    const int s = (int)(i / n_cells);
+    const bool cx = minx[i] == maxx[i];
+    const double mx = cx ? key_to_f64(minx[i]) : sx[i] / (double)c;
+    mean_x[i] = mx;
+    const_x[i] = cx;
+    if (fx_of_sel[s] == fy_of_sel[s]) {
+      mean_y[i] = mx;
+      const_y[i] = cx;
+    } else {
+      const bool cy = miny[i] == maxy[i];
+      mean_y[i] = cy ? key_to_f64(miny[i]) : sy[i] / (double)c;
+      const_y[i] = cy;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) moments_centred_kernel(
+    const int32_t* __restrict__ cell,
+    const double* __restrict__ fields, int64_t field_stride,
+    const int32_t* __restrict__ field_idx, int n_field_rows,
+    const int32_t* __restrict__ fx_of_sel, const int32_t* __restrict__ fy_of_sel,
+    int M, int64_t n, int n_cells, int lds_cap,
+    const double* __restrict__ mean_x, const double* __restrict__ mean_y,
+    double* __restrict__ out_m2x, double* __restrict__ out_m2y,
+    double* __restrict__ out_cxy) {
+  __shared__ int32_t s_lo, s_hi;
+  __shared__ unsigned int s_cnt[LDS_CELLS];
+  __shared__ double s_m2x[LDS_CELLS];
+  __shared__ double s_m2y[LDS_CELLS];
+  __shared__ double s_cxy[LDS_CELLS];
+  const int tid = threadIdx.x;
+  const int nthreads = blockDim.x;
+  const int64_t ntiles = (n + AGG_TILE - 1) / AGG_TILE;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t t0 = tile * AGG_TILE;
+    const int64_t t1 = min(t0 + (int64_t)AGG_TILE, n);
+    int32_t lo, hi;
+    if (!moments_tile_span(cell, t0, t1, n_cells, &s_lo, &s_hi, lo, hi)) continue;
+    const int range = hi - lo + 1;
+    const bool in_lds = range <= lds_cap;
+    for (int s = 0; s < M; s++) {
+      const int32_t rx = field_idx[fx_of_sel[s]];
+      const int32_t ry = field_idx[fy_of_sel[s]];
+      if (rx < 0 || rx >= n_field_rows || ry < 0 || ry >= n_field_rows)
+        continue;                                          // block-uniform
+      const bool same = fx_of_sel[s] == fy_of_sel[s];
+      const double* __restrict__ colx = fields + (int64_t)rx * field_stride;
+      const double* __restrict__ coly = fields + (int64_t)ry * field_stride;
+      const int64_t sbase = (int64_t)s * n_cells;
+      if (in_lds) {
+        for (int k = tid; k < range; k += nthreads) {
+          s_cnt[k] = 0u; s_m2x[k] = 0.0; s_m2y[k] = 0.0; s_cxy[k] = 0.0;
+        }
+        __syncthreads();
+        for (int64_t i = t0 + tid; i < t1; i += nthreads) {
+          const int32_t c = cell[i];
+          if (c < 0 || c >= n_cells) continue;
+          const double x = colx[i];
+          const double y = same ? x : coly[i];
+          if (isnan(x) || isnan(y)) continue;
+          const int k = c - lo;
+          const double dx = x - mean_x[sbase + c];
+          atomicAdd(&s_cnt[k], 1u);
+          atomicAdd(&s_m2x[k], dx * dx);
+          if (!same) {
+            const double dy = y - mean_y[sbase + c];
+            atomicAdd(&s_m2y[k], dy * dy);
+            atomicAdd(&s_cxy[k], dx * dy);
+          }
+        }
+        __syncthreads();
+        for (int k = tid; k < range; k += nthreads) {
+          if (!s_cnt[k]) continue;
+          const int64_t o = sbase + lo + k;
+          atomicAdd(&out_m2x[o], s_m2x[k]);
+          if (!same) {
+            atomicAdd(&out_m2y[o], s_m2y[k]);
+            atomicAdd(&out_cxy[o], s_cxy[k]);
+          }
+        }
+        __syncthreads();
+      } else {
+        for (int64_t i = t0 + tid; i < t1; i += nthreads) {
+          const int32_t c = cell[i];
+          if (c < 0 || c >= n_cells) continue;
+          const double x = colx[i];
+          const double y = same ? x : coly[i];
+          if (isnan(x) || isnan(y)) continue;
+          const int64_t o = sbase + c;
+          const double dx = x - mean_x[o];
+          atomicAdd(&out_m2x[o], dx * dx);
+          if (!same) {
+            const double dy = y - mean_y[o];
+            atomicAdd(&out_m2y[o], dy * dy);
+            atomicAdd(&out_cxy[o], dx * dy);
+          }
+        }
+      }
+    }
+  }
+}
+
 // ------------------------------------------------- K16 scatter append
 /// One launch appends a routed wire batch into MULTIPLE region memtables:
 // row i goes to region region_of[i] at row dst_off[i]. Replaces per-region
@@ -1280,6 +1561,12 @@ static inline int qsel_grid(int64_t n) {
   return (int)max(min(ntiles, (int64_t)QSEL_MAX_GRID), (int64_t)1);
 }
 
+// one block per AGG_TILE rows, like the bucket aggregate
+static inline int moments_grid(int64_t n) {
+  const int64_t ntiles = (n + AGG_TILE - 1) / AGG_TILE;
+  return (int)max(min(ntiles, (int64_t)8192), (int64_t)1);
+}
+
 }  // namespace gdb_hip
 
 void gdb_hip::launch_decode_minmax(
@@ -1431,6 +1718,44 @@ void gdb_hip::launch_quantile_finish(
     double* out_lo, double* out_hi, hipStream_t stream) {
   hipLaunchKernelGGL(quantile_finish_kernel, dim3(grid_for(QC, 256)), dim3(256),
       0, stream, prefix, k1, cnt, le, next, QC, out_lo, out_hi);
+}
+
+void gdb_hip::launch_moments_sums(
+    const int32_t* cell, const double* fields, int64_t field_stride,
+    const int32_t* field_idx, int n_field_rows, const int32_t* fx_of_sel,
+    const int32_t* fy_of_sel, int M, int64_t n, int n_cells, int lds_cap,
+    unsigned long long* cnt, double* sx, double* sy,
+    unsigned long long* minx, unsigned long long* maxx,
+    unsigned long long* miny, unsigned long long* maxy, hipStream_t stream) {
+  lds_cap = min(lds_cap, LDS_CELLS);
+  hipLaunchKernelGGL(moments_sums_kernel, dim3(moments_grid(n)), dim3(256), 0,
+      stream, cell, fields, field_stride, field_idx, n_field_rows, fx_of_sel,
+      fy_of_sel, M, n, n_cells, lds_cap, cnt, sx, sy, minx, maxx, miny, maxy);
+}
+
+void gdb_hip::launch_moments_mean(
+    const unsigned long long* cnt, const double* sx, const double* sy,
+    const unsigned long long* minx, const unsigned long long* maxx,
+    const unsigned long long* miny, const unsigned long long* maxy,
+    const int32_t* fx_of_sel, const int32_t* fy_of_sel, int n_cells,
+    int64_t MC, double* mean_x, double* mean_y, bool* const_x, bool* const_y,
+    hipStream_t stream) {
+  hipLaunchKernelGGL(moments_mean_kernel, dim3(grid_for(MC, 256)), dim3(256),
+      0, stream, cnt, sx, sy, minx, maxx, miny, maxy, fx_of_sel, fy_of_sel,
+      n_cells, MC, mean_x, mean_y, const_x, const_y);
+}
+
+void gdb_hip::launch_moments_centred(
+    const int32_t* cell, const double* fields, int64_t field_stride,
+    const int32_t* field_idx, int n_field_rows, const int32_t* fx_of_sel,
+    const int32_t* fy_of_sel, int M, int64_t n, int n_cells, int lds_cap,
+    const double* mean_x, const double* mean_y, double* m2x, double* m2y,
+    double* cxy, hipStream_t stream) {
+  lds_cap = min(lds_cap, LDS_CELLS);
+  hipLaunchKernelGGL(moments_centred_kernel, dim3(moments_grid(n)), dim3(256),
+      0, stream, cell, fields, field_stride, field_idx, n_field_rows,
+      fx_of_sel, fy_of_sel, M, n, n_cells, lds_cap, mean_x, mean_y, m2x, m2y,
+      cxy);
 }
 
 void gdb_hip::launch_rle_expand_indices(

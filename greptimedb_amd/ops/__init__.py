@@ -12,9 +12,11 @@ from greptimedb_amd.ops.kernels import (  # noqa: F401
     dedup_mark_last,
     filter_series_time,
     gorilla_encode,
+    grouped_moments,
     grouped_quantile,
     hip_ops_available,
     merge_last_non_null,
+    moments_finish,
     prom_range_eval,
     quantile_lerp,
     series_last,

@@ -149,6 +149,115 @@ def quantile_lerp(lo, hi, cnt, p):
     return np.where(cnt > 0, out, np.nan)
 
 
+def pair_moments(x, y):
+    """Two-pass second moments of paired float64 arrays without NaN →
+    (n, mean_x, mean_y, m2x, m2y, cxy, const_x, const_y). m2 = Σ(x−x̄)²,
+    cxy = Σ(x−x̄)(y−ȳ). A column is constant when min == max; its mean is
+    then the value itself and its m2 (and cxy) exactly 0. n == 0: NaN means,
+    zero sums, flags clear."""
+    import numpy as np
+    n = len(x)
+    if n == 0:
+        return 0, np.nan, np.nan, 0.0, 0.0, 0.0, False, False
+    cx = bool(x.min() == x.max())
+    cy = bool(y.min() == y.max())
+    mx = float(x[0]) if cx else float(x.sum() / n)
+    my = float(y[0]) if cy else float(y.sum() / n)
+    with np.errstate(invalid="ignore"):
+        dx = x - mx
+        dy = y - my
+        m2x = 0.0 if cx else float((dx * dx).sum())
+        m2y = 0.0 if cy else float((dy * dy).sum())
+        cxy = 0.0 if (cx or cy) else float((dx * dy).sum())
+    return n, mx + 0.0, my + 0.0, m2x, m2y, cxy, cx, cy
+
+
+def grouped_moments(sources, fx_of_sel, fy_of_sel, n_cells):
+    """Grouped second moments. sources as for grouped_quantile; selection s
+    pairs field rows field_idx[fx_of_sel[s]] and field_idx[fy_of_sel[s]]
+    (fx == fy is the one-argument form). A row counts in its cell where the
+    cell id lies in [0, n_cells) and neither value is NaN. Returns, each
+    [M, n_cells]: n i64, mean_x, mean_y, m2x, m2y, cxy f64, const_x, const_y
+    bool, per cell as pair_moments defines them."""
+    import numpy as np
+    M = len(fx_of_sel)
+    if M < 1 or len(fy_of_sel) != M:
+        raise ValueError("grouped_moments: one (x, y) pair per selection, at least one")
+    if n_cells < 1 or M * n_cells > MAX_QUANTILE_CELLS:
+        raise RuntimeError(f"grouped_moments: M * n_cells = {M} * {n_cells} "
+                           f"exceeds {MAX_QUANTILE_CELLS}")
+    for _c, _f, fidx in sources:
+        for f in list(fx_of_sel) + list(fy_of_sel):
+            if not 0 <= int(f) < int(fidx.numel()):
+                raise RuntimeError(f"grouped_moments: selection field {f} "
+                                   f"outside field_idx of length {fidx.numel()}")
+    cnt = np.zeros((M, n_cells), dtype=np.int64)
+    mean = np.full((2, M, n_cells), np.nan)
+    acc = np.zeros((3, M, n_cells))
+    const = np.zeros((2, M, n_cells), dtype=bool)
+    for s in range(M):
+        cells, xs, ys = [], [], []
+        for cell, fields, fidx in sources:
+            m = int(cell.numel())
+            if m == 0:
+                continue
+            cells.append(cell.numpy())
+            xs.append(fields[int(fidx[fx_of_sel[s]])][:m].numpy())
+            ys.append(fields[int(fidx[fy_of_sel[s]])][:m].numpy())
+        if not cells:
+            continue
+        c = np.concatenate(cells)
+        x = np.concatenate(xs)
+        y = np.concatenate(ys)
+        ok = (c >= 0) & (c < n_cells) & ~np.isnan(x) & ~np.isnan(y)
+        c, x, y = c[ok], x[ok], y[ok]
+        order = np.argsort(c, kind="stable")
+        c, x, y = c[order], x[order], y[order]
+        ids, starts = np.unique(c, return_index=True)
+        ends = np.append(starts[1:], len(c))
+        for ci, a, b in zip(ids.tolist(), starts.tolist(), ends.tolist()):
+            (cnt[s, ci], mean[0, s, ci], mean[1, s, ci], acc[0, s, ci],
+             acc[1, s, ci], acc[2, s, ci], const[0, s, ci],
+             const[1, s, ci]) = pair_moments(x[a:b], y[a:b])
+    t = torch.from_numpy
+    return (t(cnt), t(mean[0]), t(mean[1]), t(acc[0]), t(acc[1]), t(acc[2]),
+            t(const[0]), t(const[1]))
+
+
+MOMENT_KINDS = {"var_pop": 1, "var_samp": 1, "stddev_pop": 1, "stddev_samp": 1,
+                "covar_pop": 2, "covar_samp": 2, "covar": 2, "corr": 2}
+
+
+def moments_finish(kind, planes):
+    """Final SQL value of moment aggregate `kind` from grouped_moments'
+    planes (numpy arrays of any common shape) → (values f64, null bool).
+      var_pop, stddev_pop  M2x/n, sqrt           NULL when n = 0
+      var_samp, stddev_samp  M2x/(n−1), sqrt     NULL when n < 2
+      covar_pop            C/n                   NULL when n = 0
+      covar_samp, covar    C/(n−1)               NULL when n < 2
+      corr                 C/sqrt(M2x·M2y) clamped to [−1, 1]; NULL when
+                           n < 2 or x or y is constant (PostgreSQL's rule)
+    Values are NaN where null."""
+    import numpy as np
+    n, _mx, _my, m2x, m2y, cxy, cx, cy = [np.asarray(p) for p in planes]
+    if kind not in MOMENT_KINDS:
+        raise ValueError(f"unknown moment aggregate {kind}")
+    nf = n.astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        if kind in ("var_pop", "stddev_pop", "covar_pop"):
+            null = n == 0
+            out = (cxy if kind == "covar_pop" else m2x) / nf
+        elif kind == "corr":
+            null = (n < 2) | cx | cy
+            out = np.clip(cxy / np.sqrt(m2x * m2y), -1.0, 1.0)
+        else:
+            null = n < 2
+            out = (cxy if kind in ("covar_samp", "covar") else m2x) / (nf - 1.0)
+        if kind.startswith("stddev"):
+            out = np.sqrt(out)
+    return np.where(null, np.nan, out), null
+
+
 def filter_series_time(ts, series, slot_lut, ts_lo, ts_hi):
     keep = (ts >= ts_lo) & (ts < ts_hi)
     if slot_lut is not None and slot_lut.numel() > 0:

@@ -109,6 +109,27 @@ def grouped_quantile(sources, field_of_sel, p_of_sel, n_cells, on_pass=None,
 quantile_lerp = cpu_ref.quantile_lerp
 
 
+def grouped_moments(sources, fx_of_sel, fy_of_sel, n_cells, lds_cells=1024):
+    """Grouped second moments over [(cell, fields, field_idx)] sources →
+    (n, mean_x, mean_y, m2x, m2y, cxy, const_x, const_y), each [M, n_cells]
+    (see cpu_ref.grouped_moments; cpu_ref.moments_finish turns them into
+    var / stddev / covar / corr values and their NULL masks). On GPU: one
+    pass for counts, sums and min/max, one for the sums centred on the means,
+    no host sync between them. `lds_cells` (GPU only) caps the cell span a
+    row tile may have to accumulate in LDS; 0 forces global atomics.
+    `field_idx` entries must be valid rows of `fields`, as for
+    grouped_quantile."""
+    sources = list(sources)
+    if sources and sources[0][0].is_cuda:
+        return tuple(_require_hip().grouped_moments(
+            sources, [int(f) for f in fx_of_sel], [int(f) for f in fy_of_sel],
+            int(n_cells), int(lds_cells)))
+    return cpu_ref.grouped_moments(sources, fx_of_sel, fy_of_sel, n_cells)
+
+
+moments_finish = cpu_ref.moments_finish
+
+
 def filter_series_time(ts, series, slot_lut, ts_lo, ts_hi):
     if ts.is_cuda:
         ops = _require_hip()

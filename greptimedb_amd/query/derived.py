@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from greptimedb_amd.ops.cpu_ref import MOMENT_KINDS as _MOMENT_KINDS
 from greptimedb_amd.query import ast
 from greptimedb_amd.utils.errors import PlanQuery
 
@@ -22,7 +23,10 @@ AGGS = {"count", "sum", "min", "max", "avg", "mean", "last_value",
         "first_value", "stddev", "var",
         # sketch/approx aggregates (reference aggrs/approximate)
         "hll", "hll_merge", "uddsketch_state", "uddsketch_merge",
-        "approx_percentile", "median"}
+        "approx_percentile", "median",
+        # two-pass second moments (ops.cpu_ref.MOMENT_KINDS)
+        "var_pop", "var_samp", "stddev_pop", "stddev_samp",
+        "covar_pop", "covar_samp", "covar", "corr"}
 
 SKETCH_SCALARS = {"hll_count", "uddsketch_calc"}
 
@@ -72,6 +76,29 @@ def _agg_value(fname: str, vals: np.ndarray):
             "first_value": lambda x: x[0]}[fname](v)
 
 
+def _float_or_nan(vals: np.ndarray) -> np.ndarray:
+    if vals.dtype == object:
+        return np.array([np.nan if v is None else v for v in vals],
+                        dtype=np.float64)
+    return vals.astype(np.float64)
+
+
+def _moment_value(fn: str, e, col_data: dict, rows: np.ndarray):
+    """var_* / stddev_* / covar_* / corr over the rows of one group: the
+    rows in which every argument is non-NULL, two-pass in float64, with the
+    NULL rules of cpu_ref.moments_finish."""
+    from greptimedb_amd.ops import cpu_ref
+    from greptimedb_amd.query import executor as X
+    if len(e.args) != _MOMENT_KINDS[fn] or e.distinct:
+        raise PlanQuery(f"{fn} takes {_MOMENT_KINDS[fn]} plain argument(s)")
+    cols = [_float_or_nan(np.atleast_1d(np.asarray(X._np_raw(a, col_data)))[rows])
+            for a in e.args]
+    x, y = cols[0], cols[-1]
+    ok = ~np.isnan(x) & ~np.isnan(y)
+    val, null = cpu_ref.moments_finish(fn, cpu_ref.pair_moments(x[ok], y[ok]))
+    return None if bool(null) else float(val)
+
+
 def _eval_scalar(e, col_data: dict, rows: np.ndarray):
     """Evaluate an expression (possibly containing aggregates) over the
     row subset `rows` to a scalar (aggregate context)."""
@@ -111,6 +138,8 @@ def _eval_scalar(e, col_data: dict, rows: np.ndarray):
         fv = vals.astype(np.float64)
         fv = fv[~np.isnan(fv)]
         return float(np.quantile(fv, p)) if len(fv) else None
+    if fn in _MOMENT_KINDS:
+        return _moment_value(fn, e, col_data, rows)
     if fn in SKETCH_SCALARS:
         from greptimedb_amd.query.sketches import hll_count, uddsketch_calc
         if fn == "hll_count":

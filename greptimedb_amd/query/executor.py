@@ -32,6 +32,7 @@ from greptimedb_amd.utils.errors import (InvalidArguments, PlanQuery,
                                          TableAlreadyExists, TableNotFound)
 from greptimedb_amd.utils.timeutil import parse_ts_ms, trunc_unit_ms
 from greptimedb_amd.ops import filter_series_time, ts_bucket_agg
+from greptimedb_amd.ops.cpu_ref import MOMENT_KINDS
 
 AGG_FUNCS = {"count", "sum", "min", "max", "avg", "mean", "last_value",
              "first_value"}
@@ -88,6 +89,10 @@ class _DeviceQuantilePlan:
     n_group: int               # hidden GROUP BY projections
     order_desc: list           # DESC flag per hidden ORDER BY projection
     null_fields: list          # fields with a hidden count() projection
+    m_calls: list = dfield(default_factory=list)   # repr of each moment call
+    m_kinds: list = dfield(default_factory=list)   # its function name
+    m_sel_of_call: list = dfield(default_factory=list)  # index into m_pairs
+    m_pairs: list = dfield(default_factory=list)   # distinct (x, y) fields
 
 
 @dataclass
@@ -106,6 +111,12 @@ class SelectPlan:
     having: ast.Expr | None
     limit: int | None
     offset: int | None
+
+
+def _moment_null_marker(i: int) -> "ast.Func":
+    """Hidden projection that carries the NULL mask of the i-th moment call
+    of a device plan through _finalize_agg (no SQL function has this name)."""
+    return ast.Func("__moment_null", [ast.Lit(i)])
 
 
 def _split_conjuncts(e: ast.Expr) -> list[ast.Expr]:
@@ -886,9 +897,13 @@ class Executor:
                              f"{(_time.perf_counter() - t0) * 1000:.3f} ms")
             return QueryResult(["plan"], [lines])
         lines = []
-        if dq is not None:
-            path = (f"grouped-quantile (radix select, Q={len(dq.p_of_sel)}, "
+        if dq is not None and not dq.calls:
+            path = (f"grouped-moments (two-pass, M={len(dq.m_pairs)}, "
                     f"cells={dq.n_slots * dq.grid[4]})")
+        elif dq is not None:
+            moments = f", moments M={len(dq.m_pairs)}" if dq.m_pairs else ""
+            path = (f"grouped-quantile (radix select, Q={len(dq.p_of_sel)}, "
+                    f"cells={dq.n_slots * dq.grid[4]}{moments})")
         elif any(_has_range_agg(x) for x, _a in e.stmt.projections):
             path = "range-select (sliding-window kernel)"
         elif any(_collect_window_nodes(x, w := []) or w
@@ -1381,8 +1396,13 @@ class Executor:
                                for e, a in sel.projections]
             sel.where = self._resolve_subqueries(sel.where, sel)
             sel.having = self._resolve_subqueries(sel.having, sel)
+        has_moments = isinstance(sel.table, str) and \
+            sel.table in self.engine.tables and \
+            self._has_sketch_agg(sel, self._MOMENT_AGGS)
+        if has_moments and sel.joins:
+            return self._exec_join_aggregate(sel)
         if isinstance(sel.table, str) and sel.table in self.engine.tables \
-                and self._has_sketch_agg(sel):
+                and (has_moments or self._has_sketch_agg(sel)):
             dq = self._plan_device_quantile(sel)
             if dq is not None:
                 try:
@@ -1855,10 +1875,17 @@ class Executor:
                     "approx_percentile", "median", "hll_count",
                     "uddsketch_calc"}
 
-    def _has_sketch_agg(self, sel) -> bool:
+    # two-pass second-moment aggregates -> argument count
+    _MOMENT_AGGS = MOMENT_KINDS
+
+    def _has_sketch_agg(self, sel, names=None) -> bool:
+        """Whether projections or HAVING call one of `names` (default: the
+        sketch aggregates); such statements leave the fused planner."""
+        names = self._SKETCH_AGGS if names is None else names
+
         def walk(e):
             if isinstance(e, ast.Func):
-                if e.name.lower() in self._SKETCH_AGGS:
+                if e.name.lower() in names:
                     return True
                 return any(walk(a) for a in e.args)
             if isinstance(e, ast.BinOp):
@@ -1868,6 +1895,29 @@ class Executor:
             return False
         return any(walk(e) for e, _a in sel.projections) or \
             (sel.having is not None and walk(sel.having))
+
+    def _exec_join_aggregate(self, sel: ast.Select) -> QueryResult:
+        """Moment aggregates over a JOIN: the join runs as a plain select of
+        every referenced column and the derived evaluator aggregates its
+        rows, as _exec_sketch_select does for a single table."""
+        import dataclasses
+
+        from greptimedb_amd.query.derived import select_over_result
+        aliases = {a for _e, a in sel.projections if a}
+        exprs = [e for e, _a in sel.projections] + list(sel.group_by) + \
+            [e for e, _d in sel.order_by]
+        if sel.having is not None:
+            exprs.append(sel.having)
+        needed = sorted(set().union(*[_expr_cols(e) for e in exprs]) - aliases)
+        if not needed:
+            raise PlanQuery("aggregate over a JOIN references no column")
+        inner = ast.Select(projections=[(ast.Col(c), None) for c in needed],
+                           table=sel.table, table_alias=sel.table_alias,
+                           joins=sel.joins, where=sel.where)
+        base = self._exec_join(inner)
+        outer = dataclasses.replace(sel, table=None, table_alias=None,
+                                    joins=[], where=None)
+        return select_over_result(outer, base)
 
     def _exec_sketch_select(self, sel: ast.Select) -> QueryResult:
         """Sketch/approx aggregates (hll / uddsketch / approx_percentile):
@@ -1971,20 +2021,24 @@ class Executor:
 
     # ------------------------------------------- device percentiles (K21)
 
-    # Class switch, like Ingestor._fused: False keeps approx_percentile /
-    # median on the materialising host path (_exec_sketch_select).
+    # Class switches, like Ingestor._fused: False keeps approx_percentile /
+    # median, respectively the var / stddev / covar / corr family, on the
+    # materialising host path (_exec_sketch_select).
     _device_quantile = True
+    _device_moments = True
 
     def _plan_device_quantile(self, sel: ast.Select):
-        """Device plan for approx_percentile(field, p) / median(field)
+        """Device plan for approx_percentile(field, p) / median(field) and
+        the moment aggregates (var_pop(field) ... corr(field, field)),
         grouped by tags and/or one time bucket, or None when the statement
         has to stay on the host path. Nothing is scanned here."""
         import dataclasses
         from greptimedb_amd.ops.cpu_ref import MAX_QUANTILE_CELLS
-        if not self._device_quantile or self.dist is not None:
+        if self.dist is not None:
             return None
         if not (isinstance(sel.table, str) and sel.table in self.engine.tables
-                and self._has_sketch_agg(sel)):
+                and (self._has_sketch_agg(sel) or
+                     self._has_sketch_agg(sel, self._MOMENT_AGGS))):
             return None
         if sel.joins or sel.distinct or sel.ctes or sel.align_ms is not None:
             return None
@@ -1994,6 +2048,7 @@ class Executor:
             set(st.regions[0].field_names)
 
         sels: dict[str, tuple[str, float]] = {}   # repr(call) -> (field, p)
+        moms: dict[str, tuple[str, str, str]] = {}  # repr(call) -> (fn, x, y)
         agg_args: set = set()      # fields under sum/avg/min/max
 
         def walk(e, in_agg):
@@ -2007,6 +2062,14 @@ class Executor:
             if not isinstance(e, ast.Func):
                 return False
             fn = e.name.lower()
+            if fn in self._MOMENT_AGGS:
+                if in_agg or e.distinct or len(e.args) != self._MOMENT_AGGS[fn]:
+                    return False
+                if not all(isinstance(a, ast.Col) and a.name in float_fields
+                           for a in e.args):
+                    return False
+                moms[repr(e)] = (fn, e.args[0].name, e.args[-1].name)
+                return True
             if fn in self._SKETCH_AGGS:
                 if in_agg or e.distinct or fn not in ("approx_percentile", "median"):
                     return False
@@ -2048,7 +2111,10 @@ class Executor:
         exprs = [e for e, _a in sel.projections] + [e for e, _d in order_by]
         if sel.having is not None:
             exprs.append(sel.having)
-        if not all(walk(e, False) for e in exprs) or not sels:
+        if not all(walk(e, False) for e in exprs) or not (sels or moms):
+            return None
+        if (sels and not self._device_quantile) or \
+                (moms and not self._device_moments):
             return None
         if any(_has_range_agg(e) for e in exprs) or \
                 any(_collect_window_nodes(e, w := []) or w for e in exprs):
@@ -2058,10 +2124,15 @@ class Executor:
         # result is ordered afterwards the way the host path orders it. One
         # hidden count(field) per aggregated field tells NULL (no value in
         # the group) from a NaN that the arithmetic produced.
+        # A moment call's NULL mask is pairwise, so it travels as a plane of
+        # its own: one hidden marker call per moment call, which
+        # _exec_device_quantile resolves through extra_planes.
         null_fields = sorted({f for f, _p in sels.values()} | agg_args)
+        m_calls = list(moms)
         hidden = [(g, None) for g in group_by] + \
             [(e, None) for e, _d in order_by] + \
-            [(ast.Func("count", [ast.Col(f)]), None) for f in null_fields]
+            [(ast.Func("count", [ast.Col(f)]), None) for f in null_fields] + \
+            [(_moment_null_marker(i), None) for i in range(len(m_calls))]
         sel2 = dataclasses.replace(
             sel, projections=list(sel.projections) + hidden, group_by=group_by,
             order_by=[], limit=None, offset=None)
@@ -2091,7 +2162,8 @@ class Executor:
             if isinstance(e, ast.UnaryOp):
                 return finalizable(e.operand)
             if isinstance(e, ast.Func):
-                return repr(e) in sels or e.name in AGG_FUNCS or (
+                return repr(e) in sels or repr(e) in moms or \
+                    e.name in AGG_FUNCS or (
                     plan.bucket_expr is not None and
                     _same_expr(e, plan.bucket_expr))
             return False
@@ -2100,7 +2172,8 @@ class Executor:
         group_keys, region_luts = self._build_group_luts(st, plan, plan.group_tags)
         n_slots = max(len(group_keys), 1)
         calls = list(sels)
-        if len(calls) * n_slots * grid[4] > MAX_QUANTILE_CELLS:
+        m_pairs = sorted({(x, y) for _fn, x, y in moms.values()})
+        if max(len(calls), len(m_pairs)) * n_slots * grid[4] > MAX_QUANTILE_CELLS:
             return None
         return _DeviceQuantilePlan(
             sel=sel, sel2=sel2, plan=plan, grid=grid, group_keys=group_keys,
@@ -2108,15 +2181,20 @@ class Executor:
             field_of_call=[sels[c][0] for c in calls],
             p_of_sel=[sels[c][1] for c in calls],
             n_group=len(group_by), order_desc=[d for _e, d in order_by],
-            null_fields=null_fields)
+            null_fields=null_fields, m_calls=m_calls,
+            m_kinds=[moms[c][0] for c in m_calls],
+            m_sel_of_call=[m_pairs.index(moms[c][1:]) for c in m_calls],
+            m_pairs=m_pairs)
 
     def _exec_device_quantile(self, dq) -> QueryResult:
-        """Percentiles where the data lives: per source one bucket-cell pass
-        feeds both the fused aggregate (ordinary aggregates, row counts) and
-        the radix-histogram selection; only [Q, cells] planes reach the host.
+        """Percentiles and moments where the data lives: per source one
+        bucket-cell pass feeds the fused aggregate (ordinary aggregates, row
+        counts), the radix-histogram selection and the two-pass moments; only
+        [Q, cells] and [M, cells] planes reach the host.
         Output mirrors _exec_sketch_select: names, kinds, float-or-None
         values, rows ordered by group key unless ORDER BY says otherwise."""
-        from greptimedb_amd.ops import (bucket_cells, grouped_quantile,
+        from greptimedb_amd.ops import (bucket_cells, grouped_moments,
+                                        grouped_quantile, moments_finish,
                                         quantile_lerp, ts_bucket_agg_acc,
                                         ts_bucket_agg_finish)
         from greptimedb_amd.query.derived import _contains_agg, _name_of
@@ -2126,9 +2204,11 @@ class Executor:
         ts_lo, ts_hi, origin, bucket_ms, n_buckets = dq.grid
         n_slots = dq.n_slots
         agg_fields = sorted({a.arg for a in plan.aggs if a.arg is not None} |
-                            set(dq.field_of_call))
+                            set(dq.field_of_call) |
+                            {f for pair in dq.m_pairs for f in pair})
         nf = len(agg_fields)
         field_of_sel = [agg_fields.index(f) for f in dq.field_of_call]
+        n_q, n_m = len(dq.calls), len(dq.m_calls)
 
         # The cell ids (4 B per row) and, for merge-mode or residual-filtered
         # regions, the deduplicated field copies of every source stay alive
@@ -2154,18 +2234,36 @@ class Executor:
             mins = np.full((nf,) + shape, np.nan)
             maxs = np.full((nf,) + shape, np.nan)
             rowcnt = np.zeros(shape, dtype=np.int64)
-            qvals = np.full((len(dq.calls),) + shape, np.nan)
+            qvals = np.full((n_q,) + shape, np.nan)
+            mvals = np.full((n_m,) + shape, np.nan)
+            mnull = np.ones((n_m,) + shape)
         else:
-            lo, hi, cnt = grouped_quantile(
-                sources, field_of_sel, dq.p_of_sel, n_slots * n_buckets,
-                on_pass=self._cancel_check)
+            qvals = np.full((n_q,) + shape, np.nan)
+            if n_q:
+                lo, hi, cnt = grouped_quantile(
+                    sources, field_of_sel, dq.p_of_sel, n_slots * n_buckets,
+                    on_pass=self._cancel_check)
+                qvals = quantile_lerp(lo.cpu().numpy(), hi.cpu().numpy(),
+                                      cnt.cpu().numpy(), dq.p_of_sel)
+                qvals = qvals.reshape((n_q,) + shape)
+            mvals = np.full((n_m,) + shape, np.nan)
+            mnull = np.ones((n_m,) + shape)
+            if n_m:
+                planes = [t.cpu().numpy() for t in grouped_moments(
+                    sources, [agg_fields.index(x) for x, _y in dq.m_pairs],
+                    [agg_fields.index(y) for _x, y in dq.m_pairs],
+                    n_slots * n_buckets)]
+                for i, (kind, s) in enumerate(zip(dq.m_kinds, dq.m_sel_of_call)):
+                    val, null = moments_finish(kind, [p[s] for p in planes])
+                    mvals[i] = val.reshape(shape)
+                    mnull[i] = null.reshape(shape)
             sums, cnts, mins, maxs, rowcnt = [
                 t.cpu().numpy() for t in ts_bucket_agg_finish(acc)]
-            qvals = quantile_lerp(lo.cpu().numpy(), hi.cpu().numpy(),
-                                  cnt.cpu().numpy(), dq.p_of_sel)
-            qvals = qvals.reshape((len(dq.calls),) + shape)
         del sources
         plane_of = {c: qvals[i] for i, c in enumerate(dq.calls)}
+        plane_of.update({c: mvals[i] for i, c in enumerate(dq.m_calls)})
+        plane_of.update({repr(_moment_null_marker(i)): mnull[i]
+                         for i in range(n_m)})
         field_of = dict(zip(dq.calls, dq.field_of_call))
 
         res = self._finalize_agg(
@@ -2181,6 +2279,8 @@ class Executor:
         gcols = cols[n_vis:n_vis + dq.n_group]
         o0 = n_vis + dq.n_group
         cnt_of = dict(zip(dq.null_fields, cols[o0 + n_ord:]))
+        mnull_of = dict(zip(dq.m_calls,
+                            cols[o0 + n_ord + len(dq.null_fields):]))
         alias_expr = {a: e for e, a in sel.projections if a}
 
         def null_mask(e):
@@ -2196,6 +2296,8 @@ class Executor:
                 return null_mask(e.operand)
             if isinstance(e, ast.Func) and repr(e) in field_of:
                 return cnt_of[field_of[repr(e)]] == 0
+            if isinstance(e, ast.Func) and repr(e) in mnull_of:
+                return mnull_of[repr(e)].astype(np.float64) != 0
             if isinstance(e, ast.Func) and e.name in AGG_FUNCS and \
                     e.name != "count" and isinstance(e.args[0], ast.Col):
                 return cnt_of[e.args[0].name] == 0
